@@ -8,6 +8,14 @@ per-GPU batch fixed as N grows).
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`;
 launched via torch.distributed.run for N>1. Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, optionally write the last step's outputs
+(`--dump-outputs DIR`), print the result line. Secondary measurements
+belong behind `--full` (off by default); there are none at present, so
+`--full` currently runs the same path. Model weights and the synthetic
+batch come from a fixed seed, so two runs with the same arguments see
+identical inputs and their dumped outputs can be compared array by array.
 """
 import argparse
 import json
@@ -15,6 +23,11 @@ import os
 import time
 
 import torch
+
+SEED = 20240917
+# per-array cap for --dump-outputs (16 MB as float32, so a dump stays well
+# under 64 MB); a larger array is stored as a fixed seeded sample
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
 
 
 def parse_args():
@@ -36,7 +49,30 @@ def parse_args():
                     help='hipGraph-capture the fwd+loss+bwd inner loop '
                          '(single-rank only; collectives and the optimizer '
                          'stay outside the capture)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed '
+                         'step returned to its caller (logits, loss) as '
+                         'DIR/<name>.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary measurements (none at '
+                         'present: the plain run is already headline-only)')
     return ap.parse_args()
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor as float32 `dirname/<name>.npy`. Arrays above
+    DUMP_MAX_ELEMS are flattened and reduced to a fixed seeded sample of
+    their elements (same indices every run, ascending order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(device='cpu', dtype=torch.float32).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.RandomState(SEED % (2 ** 32)).choice(
+                a.size, DUMP_MAX_ELEMS, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, name + '.npy'),
+                np.ascontiguousarray(a))
 
 
 def build_model(args, device):
@@ -111,6 +147,7 @@ def main():
         torch.cuda.set_device(device)
         torch.backends.cudnn.benchmark = True
 
+    torch.manual_seed(SEED)  # same weights + batch on every run and rank
     net, data, labels = build_model(args, device)
     comm_stream = torch.cuda.Stream() if on_gpu else None
     buf = FlatGradBuffer(net.parameters(), world_size=world,
@@ -122,6 +159,8 @@ def main():
 
     import torch.distributed as dist
 
+    last = {}  # logits/loss of the most recent fwd_bwd (static under replay)
+
     def fwd_bwd(sync):
         buf.zero_()
         buf.begin_round(sync=sync)
@@ -130,7 +169,9 @@ def main():
                 out = net(data)
             loss = ops.cross_entropy(out.float(), labels)
         else:
-            loss = ops.cross_entropy(net(data), labels)
+            out = net(data)
+            loss = ops.cross_entropy(out, labels)
+        last['logits'], last['loss'] = out.detach(), loss.detach()
         loss.backward()
 
     def one_step():
@@ -186,6 +227,15 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1000.0
     samples_per_sec = args.batch * world * args.steps / elapsed
+
+    if rank == 0 and args.dump_outputs:
+        # What the step hands its caller. They depend on every weight
+        # update of the steps before, so they cover the whole path. The
+        # weights themselves are left out: at lr 1e-3 on one fixed noise
+        # batch the early VBM layers go non-finite within ~10 steps (the
+        # fused ReLU masks them), which makes them useless for comparing.
+        dump_outputs(args.dump_outputs, {'logits': last['logits'],
+                                         'loss': last['loss']})
 
     if rank == 0:
         print(json.dumps({

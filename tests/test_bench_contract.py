@@ -11,9 +11,9 @@ REQUIRED_KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup',
                  'dtype', 'data', 'config'}
 
 
-def _run(cmd, timeout=300):
+def _run(cmd, timeout=300, env=None):
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True,
-                       timeout=timeout)
+                       timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, f'expected ONE json line, got {len(lines)}'
@@ -66,6 +66,56 @@ def test_bench_mlp_model():
     out = _run([sys.executable, 'bench.py', '--model', 'mlp', '--steps', '2',
                 '--warmup', '1', '--batch', '8'])
     assert 'mlp' in out['metric']
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy;
+    same arguments => same inputs => (on the deterministic CPU path) the
+    same outputs. --full is accepted and keeps the result line's meaning."""
+    import numpy as np
+    args = ['--model', 'mlp', '--steps', '3', '--warmup', '1', '--batch', '8']
+    # pin the CPU path (bitwise repeatable) even where a GPU is present
+    env = dict(os.environ, HIP_VISIBLE_DEVICES='', CUDA_VISIBLE_DEVICES='')
+    outs = []
+    for sub, extra in (('a', []), ('b', ['--full'])):
+        d = tmp_path / sub
+        res = _run([sys.executable, 'bench.py'] + args + extra +
+                   ['--dump-outputs', str(d)], env=env)
+        assert res['dtype'] == 'fp32'
+        assert REQUIRED_KEYS <= set(res) and res['steps'] == 3
+        assert res['ms_per_step'] > 0
+        files = sorted(os.listdir(d))
+        assert files == ['logits.npy', 'loss.npy']
+        outs.append({f: np.load(d / f) for f in files})
+    a, b = outs
+    assert a['logits.npy'].shape == (8, 2)
+    assert a['loss.npy'].size == 1
+    total = 0
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f'{f} differs between runs'
+        total += a[f].nbytes
+    assert total <= 64 * 1024 * 1024
+    assert np.abs(a['logits.npy']).max() > 0
+
+
+def test_bench_dump_sampling_is_fixed():
+    """Arrays above the per-array cap are stored as the same seeded sample
+    of their elements on every call."""
+    import numpy as np
+    import tempfile
+    import torch
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    with tempfile.TemporaryDirectory() as d:
+        bench.dump_outputs(d, {'big': big, 'small': big[:10].view(2, 5)})
+        first = np.load(os.path.join(d, 'big.npy'))
+        bench.dump_outputs(d, {'big': big})
+        again = np.load(os.path.join(d, 'big.npy'))
+        small = np.load(os.path.join(d, 'small.npy'))
+    assert first.shape == (bench.DUMP_MAX_ELEMS,) and small.shape == (2, 5)
+    assert np.array_equal(first, again)
+    assert (np.diff(first) > 0).all()  # distinct source elements, in order
 
 
 def test_bench_torchrun_eight_ranks():

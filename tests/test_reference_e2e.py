@@ -1,136 +1,70 @@
-"""Whole-protocol differential: drive the UPSTREAM reference package's
-COINNLocal/COINNRemote through the in-process loopback relay on the SAME
-site data, seeds and hyperparameters as our stack, and require the two
-runs to agree — round count, reduced global scores, and final weights.
+"""Whole-protocol differential: the UPSTREAM reference package's
+COINNLocal/COINNRemote driven through the in-process loopback relay on the
+SAME site data, seeds and hyperparameters as our stack; the two runs must
+agree — round count, reduced global scores, and final weights.
 
 This is the strongest drop-in-compatibility statement the CPU can make:
 the same user computation (module arch, iteration math) trained by both
 frameworks converges to the same model through the same protocol.
-Skips when /root/reference is not mounted (e.g. GPU boxes).
+
+The reference side of each run is recorded in
+tests/golden/reference_e2e.json (tools/make_reference_golden.py drives the
+upstream package and writes it); our side runs live here.
 """
-import itertools
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
 TESTS_DIR = os.path.dirname(os.path.abspath(__file__))
-REF_ROOT = '/root/reference'
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(os.path.join(REF_ROOT, 'coinstac_dinunet')),
-    reason='reference mount not present')
-
 sys.path.insert(0, TESTS_DIR)
 
+import refgolden as G  # noqa: E402
 
-class _FakePool:
-    """starmap-only stand-in for the platform's multiprocessing pool."""
-
-    @staticmethod
-    def starmap(fn, iterable):
-        return list(itertools.starmap(fn, iterable))
+_KW = G.E2E_KW
 
 
-def _import_reference():
-    if 'cv2' not in sys.modules:
-        cv2 = types.ModuleType('cv2')
-        cv2.createCLAHE = lambda **kw: None
-        sys.modules['cv2'] = cv2
-    if not hasattr(np, 'float'):
-        np.float = float
-    if REF_ROOT not in sys.path:
-        sys.path.insert(0, REF_ROOT)
-    import coinstac_dinunet  # noqa: F401
+@pytest.fixture(scope='module')
+def ref():
+    """What the reference runs produced (read-only)."""
+    return G.load('reference_e2e')
 
 
-_KW = dict(task_id='tab', batch_size=4, epochs=2, validation_epochs=1,
-           local_iterations=1, split_ratio=(0.6, 0.2, 0.2), data_dir='data',
-           num_class=2, seed_all=True, patience=2, verbose=False)
-
-
-def _make_reference_classes():
-    """Reference-API computation: same module arch as our TabularTrainer."""
-    from coinstac_dinunet import COINNDataset as RefDataset
-    from coinstac_dinunet import COINNTrainer as RefTrainer
-    from coinstac_dinunet_amd.models import FreeSurferMLP
-
-    class RefTabularDataset(RefDataset):
-        def load_index(self, file):
-            self.indices.append(file)
-
-        def __getitem__(self, ix):
-            rec = np.load(os.path.join(self.state['baseDirectory'],
-                                       self.cache.get('data_dir', 'data'),
-                                       self.indices[ix]),
-                          allow_pickle=True).item()
-            return {'inputs': torch.from_numpy(rec['x']),
-                    'labels': torch.tensor(rec['y'], dtype=torch.long)}
-
-    class RefTabularTrainer(RefTrainer):
-        def _init_nn_model(self):
-            self.nn['net'] = FreeSurferMLP(in_features=16,
-                                           hidden_sizes=(32, 16),
-                                           num_class=2, dropout=0.0)
-
-        def iteration(self, batch):
-            dev = self.device.get('gpu', torch.device('cpu'))
-            inputs = batch['inputs'].to(dev).float()
-            labels = batch['labels'].to(dev).long()
-            out = self.nn['net'](inputs)
-            loss = torch.nn.functional.cross_entropy(out, labels)
-            pred = torch.argmax(out, 1)
-            avg = self.new_averages()
-            avg.add(loss.item(), len(inputs))
-            metrics = self.new_metrics()
-            metrics.add(pred, labels)
-            return {'loss': loss, 'averages': avg, 'metrics': metrics,
-                    'output': pred}
-
-    return RefTabularTrainer, RefTabularDataset
-
-
-def _run_reference(root):
-    _import_reference()
-    from coinstac_dinunet import COINNLocal as RefLocal
-    from coinstac_dinunet import COINNRemote as RefRemote
+def _cluster(root, sizes, seed):
     from coinstac_dinunet_amd.simulator import LoopbackCluster
     from computations import make_site_data
-
-    trainer_cls, dataset_cls = _make_reference_classes()
-    cluster = LoopbackCluster(
+    c = LoopbackCluster(
         root, n_sites=2,
-        site_data=lambda s: make_site_data(s.as_dict(), n_samples=20,
+        site_data=lambda s: make_site_data(s.as_dict(),
+                                           n_samples=sizes[s.clientId],
                                            seed=int(s.clientId[-1])))
-    cluster.remote_cache['seed'] = 2024  # else each package uses its own
-    success, _ = cluster.run(
-        lambda cache, input, state: RefLocal(cache=cache, input=input,
-                                             state=state, mode='train',
-                                             **_KW),
-        lambda cache, input, state: RefRemote(cache=cache, input=input,
-                                              state=state),
-        trainer_cls, dataset_cls=dataset_cls, mp_pool=_FakePool(),
-        max_rounds=400)
-    return success, cluster
+    c.remote_cache['seed'] = seed  # match the reference run's seed
+    return c
 
 
-def _run_ours(root):
+def _run_ours(cluster, kw, max_rounds, **inject):
     from coinstac_dinunet_amd import COINNLocal, COINNRemote
     from coinstac_dinunet_amd.config.keys import Mode
-    from coinstac_dinunet_amd.distrib.learner import COINNLearner
-    from coinstac_dinunet_amd.distrib.reducer import COINNReducer \
-        as COINNReducerD
-    from coinstac_dinunet_amd.simulator import LoopbackCluster
-    from computations import TabularDataset, TabularTrainer, make_site_data
+    from computations import TabularDataset, TabularTrainer
+    ok, _ = cluster.run(
+        lambda cache, input, state: COINNLocal(cache=cache, input=input,
+                                               state=state, mode=Mode.TRAIN,
+                                               **kw),
+        lambda cache, input, state: COINNRemote(cache=cache, input=input,
+                                                state=state),
+        TabularTrainer, dataset_cls=TabularDataset, max_rounds=max_rounds,
+        **inject)
+    return ok
 
-    class UnshuffledLearner(COINNLearner):
-        """The reference's padded train loader never shuffles (its
-        get_loader forces shuffle False before building the sampler,
-        data.py:163-171); ours shuffles seeded by default. Align batch
-        order for the bitwise comparison."""
 
+def _unshuffled(base):
+    """The reference's padded train loader never shuffles (its get_loader
+    forces shuffle False before building the sampler); ours shuffles
+    seeded by default. Align batch order for the bitwise comparison."""
+
+    class Unshuffled(base):
         def backward(self):
             out = {}
             self.trainer.nn[self.first_model].train()
@@ -144,40 +78,30 @@ def _run_ours(root):
                 out.update(**nxt)
             return self.trainer.reduce_iteration(its), out
 
-    cluster = LoopbackCluster(
-        root, n_sites=2,
-        site_data=lambda s: make_site_data(s.as_dict(), n_samples=20,
-                                           seed=int(s.clientId[-1])))
-    cluster.remote_cache['seed'] = 2024  # match the reference run's seed
-    success, _ = cluster.run(
-        lambda cache, input, state: COINNLocal(cache=cache, input=input,
-                                               state=state, mode=Mode.TRAIN,
-                                               agg_engine='dSGD_unshuffled',
-                                               **_KW),
-        lambda cache, input, state: COINNRemote(cache=cache, input=input,
-                                                state=state),
-        TabularTrainer, dataset_cls=TabularDataset,
-        learner_cls=UnshuffledLearner, reducer_cls=COINNReducerD,
-        max_rounds=400)
-    return success, cluster
+    return Unshuffled
 
 
-def test_reference_and_ours_agree_end_to_end(tmp_path):
-    ok_ref, ref_cluster = _run_reference(str(tmp_path / 'ref'))
-    ok_our, our_cluster = _run_ours(str(tmp_path / 'ours'))
-    assert ok_ref and ok_our
-    assert ref_cluster.rounds == our_cluster.rounds, \
+_EVEN = {'local0': 20, 'local1': 20}
+
+
+def test_reference_and_ours_agree_end_to_end(ref, tmp_path):
+    from coinstac_dinunet_amd.config.keys import Key
+    from coinstac_dinunet_amd.distrib.learner import COINNLearner
+    from coinstac_dinunet_amd.distrib.reducer import COINNReducer
+    want = ref['dsgd']
+    our_cluster = _cluster(str(tmp_path / 'ours'), _EVEN, 2024)
+    kw = dict(_KW, agg_engine='dSGD_unshuffled')
+    ok_our = _run_ours(our_cluster, kw, 400,
+                       learner_cls=_unshuffled(COINNLearner),
+                       reducer_cls=COINNReducer)
+    assert want['ok'] and ok_our
+    assert want['rounds'] == our_cluster.rounds, \
         'protocols took different numbers of rounds'
 
     # reduced global test scores agree
-    from coinstac_dinunet_amd.config.keys import Key
-    rs = ref_cluster.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
+    rs = want['global_test']
     os_ = our_cluster.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
     assert len(rs) == len(os_) == 1
-
-    def flat(x):
-        return np.asarray(x['averages'] + [x['metrics']], dtype=object)
-
     ra = np.asarray(rs[0]['averages'], dtype=float)
     oa = np.asarray(os_[0]['averages'], dtype=float)
     np.testing.assert_allclose(ra, oa, rtol=1e-5)
@@ -187,57 +111,28 @@ def test_reference_and_ours_agree_end_to_end(tmp_path):
 
     # final site models agree parameter by parameter
     for i in range(2):
-        rnet = ref_cluster.site_caches[i]['nn']['net']
         onet = our_cluster.site_caches[i]['nn']['net']
-        for (rn, rp), (on, op_) in zip(rnet.named_parameters(),
-                                       onet.named_parameters()):
+        ours = list(onet.named_parameters())
+        assert len(want['params'][i]) == len(ours)
+        for (rn, rp), (on, op_) in zip(want['params'][i], ours):
             assert rn == on
-            torch.testing.assert_close(rp, op_, rtol=1e-6, atol=1e-7)
+            torch.testing.assert_close(torch.tensor(rp, dtype=op_.dtype),
+                                       op_.detach(), rtol=1e-6, atol=1e-7)
 
 
-def test_reference_and_ours_agree_kfold(tmp_path):
+def test_reference_and_ours_agree_kfold(ref, tmp_path):
     """Same differential under 3-fold cross-validation: fold queue order,
     per-fold re-init and the fold score table must all line up."""
+    from coinstac_dinunet_amd.config.keys import Key
     kw = dict(_KW)
     kw.update(split_ratio=None, num_folds=3, epochs=1, patience=1)
+    want = ref['kfold']
 
-    _import_reference()
-    from coinstac_dinunet import COINNLocal as RefLocal
-    from coinstac_dinunet import COINNRemote as RefRemote
-    from coinstac_dinunet_amd import COINNLocal, COINNRemote
-    from coinstac_dinunet_amd.config.keys import Key, Mode
-    from coinstac_dinunet_amd.simulator import LoopbackCluster
-    from computations import TabularDataset, TabularTrainer, make_site_data
+    co = _cluster(str(tmp_path / 'ours'), {'local0': 18, 'local1': 18}, 7)
+    ok_our = _run_ours(co, kw, 700)
 
-    rtc, rdc = _make_reference_classes()
-
-    def build(which):
-        c = LoopbackCluster(
-            str(tmp_path / which), n_sites=2,
-            site_data=lambda s: make_site_data(s.as_dict(), n_samples=18,
-                                               seed=int(s.clientId[-1])))
-        c.remote_cache['seed'] = 7
-        return c
-
-    cr = build('ref')
-    ok_ref, _ = cr.run(
-        lambda cache, input, state: RefLocal(cache=cache, input=input,
-                                             state=state, mode='train', **kw),
-        lambda cache, input, state: RefRemote(cache=cache, input=input,
-                                              state=state),
-        rtc, dataset_cls=rdc, mp_pool=_FakePool(), max_rounds=700)
-
-    co = build('ours')
-    ok_our, _ = co.run(
-        lambda cache, input, state: COINNLocal(cache=cache, input=input,
-                                               state=state, mode=Mode.TRAIN,
-                                               **kw),
-        lambda cache, input, state: COINNRemote(cache=cache, input=input,
-                                                state=state),
-        TabularTrainer, dataset_cls=TabularDataset, max_rounds=700)
-
-    assert ok_ref and ok_our
-    rs = cr.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
+    assert want['ok'] and ok_our
+    rs = want['global_test']
     os_ = co.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
     assert len(rs) == len(os_) == 3  # one entry per fold, same order
     for fold_ref, fold_our in zip(rs, os_):
@@ -247,65 +142,35 @@ def test_reference_and_ours_agree_kfold(tmp_path):
         np.testing.assert_allclose(ra[1], oa[1])  # same sample counts
 
 
-def test_reference_and_ours_elect_same_pretrain_site(tmp_path):
+def test_reference_and_ours_elect_same_pretrain_site(ref, tmp_path):
     """Pretraining election (max train-data site) must agree. KNOWN
     REFERENCE DEADLOCK pinned here: when the elected site's pretraining
     never improves, the reference ships no weights_file and every site
-    spins in PRE_COMPUTATION forever (observed below); our local
-    proceeds to COMPUTATION instead (distrib/nodes/local.py). The test
-    asserts our stack finishes and that the reference either finishes
-    too or is stuck in exactly that phase."""
+    spins in PRE_COMPUTATION forever (recorded in the golden run); our
+    local proceeds to COMPUTATION instead (distrib/nodes/local.py). The
+    test asserts our stack finishes and that the reference either finished
+    too or was stuck in exactly that phase."""
+    from coinstac_dinunet_amd.config.keys import Phase
     kw = dict(_KW)
     kw.update(pretrain_args={'epochs': 1})
-
-    _import_reference()
-    from coinstac_dinunet import COINNLocal as RefLocal
-    from coinstac_dinunet import COINNRemote as RefRemote
-    from coinstac_dinunet_amd import COINNLocal, COINNRemote
-    from coinstac_dinunet_amd.config.keys import Mode
-    from coinstac_dinunet_amd.simulator import LoopbackCluster
-    from computations import TabularDataset, TabularTrainer, make_site_data
-
-    rtc, rdc = _make_reference_classes()
+    want = ref['pretrain']
     sizes = {'local0': 12, 'local1': 28}  # site 1 must win the election
 
-    def build(which):
-        c = LoopbackCluster(
-            str(tmp_path / which), n_sites=2,
-            site_data=lambda s: make_site_data(
-                s.as_dict(), n_samples=sizes[s.clientId],
-                seed=int(s.clientId[-1])))
-        c.remote_cache['seed'] = 7
-        return c
-
-    cr = build('ref')
-    ok_ref, _ = cr.run(
-        lambda cache, input, state: RefLocal(cache=cache, input=input,
-                                             state=state, mode='train', **kw),
-        lambda cache, input, state: RefRemote(cache=cache, input=input,
-                                              state=state),
-        rtc, dataset_cls=rdc, mp_pool=_FakePool(), max_rounds=60)
-    co = build('ours')
-    ok_our, _ = co.run(
-        lambda cache, input, state: COINNLocal(cache=cache, input=input,
-                                               state=state, mode=Mode.TRAIN,
-                                               **kw),
-        lambda cache, input, state: COINNRemote(cache=cache, input=input,
-                                                state=state),
-        TabularTrainer, dataset_cls=TabularDataset, max_rounds=500)
+    co = _cluster(str(tmp_path / 'ours'), sizes, 7)
+    ok_our = _run_ours(co, kw, 500)
 
     assert ok_our, 'our stack must complete the pretrain path'
-    if not ok_ref:
+    if not want['ok']:
         # the reference deadlock: every site still in PRE_COMPUTATION
-        from coinstac_dinunet.config.keys import Phase as RefPhase
-        assert cr.site_inputs[0].get('phase') == RefPhase.PRE_COMPUTATION
-    for cl in (cr, co):
-        assert cl.site_caches[1].get('pretrain') is True, \
-            'site 1 (more data) should pretrain'
-        assert cl.site_caches[0].get('pretrain') is False
+        assert want['site0_phase'] == want['phase_pre_computation']
+        assert want['site0_phase'] == G.plain(Phase.PRE_COMPUTATION)
+    ours = [co.site_caches[i].get('pretrain') for i in range(2)]
+    for flags in (want['pretrain_flags'], ours):
+        assert flags[1] is True, 'site 1 (more data) should pretrain'
+        assert flags[0] is False
 
 
-def test_reference_and_ours_agree_powersgd(tmp_path):
+def test_reference_and_ours_agree_powersgd(ref, tmp_path):
     """PowerSGD engine differential: warmup -> two-phase P/Q compression
     with error feedback and warm-started Qs must produce the same final
     model as the reference engine on identical data/seeds.
@@ -313,121 +178,46 @@ def test_reference_and_ours_agree_powersgd(tmp_path):
     Seed note: seeds where validation NEVER improves crash the REFERENCE
     at test time (missing best checkpoint, a reference bug our
     test_distributed guards); seed 5 improves at least once."""
-    kw = dict(_KW)
-    kw.update(agg_engine='powerSGD', matrix_approximation_rank=2,
-              start_powerSGD_iter=2, epochs=2)
-
-    _import_reference()
-    from coinstac_dinunet import COINNLocal as RefLocal
-    from coinstac_dinunet import COINNRemote as RefRemote
-    from coinstac_dinunet_amd import COINNLocal, COINNRemote
-    from coinstac_dinunet_amd.config.keys import Mode
     from coinstac_dinunet_amd.distrib.powersgd import (PowerSGDLearner,
                                                        PowerSGDReducer)
-    from coinstac_dinunet_amd.simulator import LoopbackCluster
-    from computations import TabularDataset, TabularTrainer, make_site_data
+    kw = dict(_KW)
+    kw.update(agg_engine='powerSGD_unshuffled',  # fall through to inject
+              matrix_approximation_rank=2, start_powerSGD_iter=2, epochs=2)
+    want = ref['powersgd']
 
-    rtc, rdc = _make_reference_classes()
+    co = _cluster(str(tmp_path / 'ours'), _EVEN, 5)
+    ok_our = _run_ours(co, kw, 500,
+                       learner_cls=_unshuffled(PowerSGDLearner),
+                       reducer_cls=PowerSGDReducer)
 
-    class UnshuffledPowerSGD(PowerSGDLearner):
-        def backward(self):
-            out = {}
-            self.trainer.nn[self.first_model].train()
-            self.trainer.optimizer[self.first_optim].zero_grad()
-            its = []
-            for _ in range(self.cache.get('local_iterations', 1)):
-                batch, nxt = self.trainer.data_handle.next_iter(shuffle=False)
-                it = self.trainer.iteration(batch)
-                it['loss'].backward()
-                its.append(it)
-                out.update(**nxt)
-            return self.trainer.reduce_iteration(its), out
-
-    def build(which):
-        c = LoopbackCluster(
-            str(tmp_path / which), n_sites=2,
-            site_data=lambda s: make_site_data(s.as_dict(), n_samples=20,
-                                               seed=int(s.clientId[-1])))
-        c.remote_cache['seed'] = 5
-        return c
-
-    cr = build('ref')
-    ok_ref, _ = cr.run(
-        lambda cache, input, state: RefLocal(cache=cache, input=input,
-                                             state=state, mode='train', **kw),
-        lambda cache, input, state: RefRemote(cache=cache, input=input,
-                                              state=state),
-        rtc, dataset_cls=rdc, mp_pool=_FakePool(), max_rounds=500)
-
-    our_kw = dict(kw)
-    our_kw['agg_engine'] = 'powerSGD_unshuffled'  # fall through to inject
-    co = build('ours')
-    ok_our, _ = co.run(
-        lambda cache, input, state: COINNLocal(cache=cache, input=input,
-                                               state=state, mode=Mode.TRAIN,
-                                               **our_kw),
-        lambda cache, input, state: COINNRemote(cache=cache, input=input,
-                                                state=state),
-        TabularTrainer, dataset_cls=TabularDataset,
-        learner_cls=UnshuffledPowerSGD, reducer_cls=PowerSGDReducer,
-        max_rounds=500)
-
-    assert ok_ref and ok_our
-    assert cr.rounds == co.rounds
+    assert want['ok'] and ok_our
+    assert want['rounds'] == co.rounds
     for i in range(2):
-        rnet = cr.site_caches[i]['nn']['net']
-        onet = co.site_caches[i]['nn']['net']
-        for rp, op_ in zip(rnet.parameters(), onet.parameters()):
-            torch.testing.assert_close(rp, op_, rtol=1e-5, atol=1e-6)
+        ours = list(co.site_caches[i]['nn']['net'].parameters())
+        assert len(want['params'][i]) == len(ours)
+        for (_, rp), op_ in zip(want['params'][i], ours):
+            torch.testing.assert_close(torch.tensor(rp, dtype=op_.dtype),
+                                       op_.detach(), rtol=1e-5, atol=1e-6)
 
 
-def test_reference_and_ours_agree_rankdad_protocol(tmp_path):
+def test_reference_and_ours_agree_rankdad_protocol(ref, tmp_path):
     """rankDAD differential (structural): same phase trajectory and round
     count. Factor VALUES legitimately differ — our power_iteration_BC
     fixes the reference's deflation (garbage components past the true
     rank; see distrib/rankdad.py docstring) — so this pins the protocol,
     not the bits."""
+    from coinstac_dinunet_amd.config.keys import Key
     kw = dict(_KW)
     kw.update(agg_engine='rankDAD', dad_reduction_rank=3, epochs=1,
               patience=1)
+    want = ref['rankdad']
 
-    _import_reference()
-    from coinstac_dinunet import COINNLocal as RefLocal
-    from coinstac_dinunet import COINNRemote as RefRemote
-    from coinstac_dinunet_amd import COINNLocal, COINNRemote
-    from coinstac_dinunet_amd.config.keys import Key, Mode
-    from coinstac_dinunet_amd.simulator import LoopbackCluster
-    from computations import TabularDataset, TabularTrainer, make_site_data
+    co = _cluster(str(tmp_path / 'ours'), _EVEN, 5)
+    ok_our = _run_ours(co, kw, 500)
 
-    rtc, rdc = _make_reference_classes()
-
-    def build(which):
-        c = LoopbackCluster(
-            str(tmp_path / which), n_sites=2,
-            site_data=lambda s: make_site_data(s.as_dict(), n_samples=20,
-                                               seed=int(s.clientId[-1])))
-        c.remote_cache['seed'] = 5
-        return c
-
-    cr = build('ref')
-    ok_ref, _ = cr.run(
-        lambda cache, input, state: RefLocal(cache=cache, input=input,
-                                             state=state, mode='train', **kw),
-        lambda cache, input, state: RefRemote(cache=cache, input=input,
-                                              state=state),
-        rtc, dataset_cls=rdc, mp_pool=_FakePool(), max_rounds=500)
-    co = build('ours')
-    ok_our, _ = co.run(
-        lambda cache, input, state: COINNLocal(cache=cache, input=input,
-                                               state=state, mode=Mode.TRAIN,
-                                               **kw),
-        lambda cache, input, state: COINNRemote(cache=cache, input=input,
-                                                state=state),
-        TabularTrainer, dataset_cls=TabularDataset, max_rounds=500)
-
-    assert ok_ref and ok_our
-    assert cr.rounds == co.rounds
-    rs = cr.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
+    assert want['ok'] and ok_our
+    assert want['rounds'] == co.rounds
+    rs = want['global_test']
     os_ = co.remote_cache[Key.GLOBAL_TEST_SERIALIZABLE]
     assert len(rs) == len(os_) == 1
     # same evaluated sample counts through the same protocol
