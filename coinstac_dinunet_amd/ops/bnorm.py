@@ -12,32 +12,60 @@ import torch.nn.functional as F
 from . import native_available, require_native
 
 
+def bn_momentum_step(bn):
+    """Count one training batch on `bn` and return the running-stat update
+    factor the way nn.BatchNorm resolves it: `momentum`, or the cumulative
+    average 1/num_batches_tracked when momentum is None. Returns None when
+    the module tracks no running stats (nothing is touched)."""
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    if bn.running_mean is None:
+        return None
+    if bn.momentum is None:
+        # reads the counter back to the host, as nn.BatchNorm does: a device
+        # sync per step, and not capturable in a hipGraph
+        return 1.0 / float(bn.num_batches_tracked)
+    return bn.momentum
+
+
+def update_running_stats(running_mean, running_var, mean, var, n, factor):
+    """running <- (1 - factor) * running + factor * batch, from the batch
+    mean and BIASED variance over n elements per channel (running_var takes
+    the unbiased estimate, as nn.BatchNorm). No-op without buffers."""
+    if running_mean is None:
+        return
+    with torch.no_grad():
+        unbiased = var * (n / max(n - 1, 1))
+        running_mean.mul_(1 - factor).add_(mean, alpha=factor)
+        running_var.mul_(1 - factor).add_(unbiased, alpha=factor)
+
+
+def _bn3d_backward(ctx, dy):
+    """Shared backward of _BN3dFn / _BN3dPreFn: grads for (x, gamma, beta);
+    every further forward argument is non-differentiable."""
+    C = require_native()
+    xb, mean_rstd, gamma, beta = ctx.saved_tensors
+    dx, dgamma, dbeta = C.bn3d_bwd(dy.to(torch.bfloat16), xb, mean_rstd,
+                                   gamma, beta, ctx.relu)
+    return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
+            dbeta.to(beta.dtype)) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
 class _BN3dFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum,
+    def forward(ctx, x, gamma, beta, running_mean, running_var, factor,
                 eps, relu):
         C = require_native()
         xb = x.to(torch.bfloat16)
         y, mean, var, mean_rstd = C.bn3d_fwd(xb, gamma, beta, eps, relu)
-        if running_mean is not None:
-            with torch.no_grad():
-                n = xb.numel() // xb.size(1)
-                unbiased = var * (n / max(n - 1, 1))
-                running_mean.mul_(1 - momentum).add_(mean, alpha=momentum)
-                running_var.mul_(1 - momentum).add_(unbiased, alpha=momentum)
+        update_running_stats(running_mean, running_var, mean, var,
+                             xb.numel() // xb.size(1), factor)
         ctx.save_for_backward(xb, mean_rstd, gamma, beta)
         ctx.relu = relu
         ctx.in_dtype = x.dtype
         return y
 
-    @staticmethod
-    def backward(ctx, dy):
-        C = require_native()
-        xb, mean_rstd, gamma, beta = ctx.saved_tensors
-        dx, dgamma, dbeta = C.bn3d_bwd(dy.to(torch.bfloat16), xb, mean_rstd,
-                                       gamma, beta, ctx.relu)
-        return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
-                dbeta.to(beta.dtype), None, None, None, None, None)
+    backward = staticmethod(_bn3d_backward)
 
 
 class _OpsBNMixin:
@@ -49,26 +77,20 @@ class _OpsBNMixin:
             y = super_forward(x)
             return F.relu(y, inplace=True) if self.relu else y
         if self.training:
-            if self.num_batches_tracked is not None:
-                self.num_batches_tracked.add_(1)
+            factor = bn_momentum_step(self)
             if getattr(x, '_coinn_bn_stats', None) is not None:
                 # stats came free from the producing conv's epilogue
                 from .conv import bn_stats_of
                 # pass x itself: .to() would drop the attached stats
                 mean, var, mean_rstd = bn_stats_of(x, self.eps)
-                if self.running_mean is not None:
-                    with torch.no_grad():
-                        n = x.numel() // x.size(1)
-                        unbiased = var * (n / max(n - 1, 1))
-                        self.running_mean.mul_(1 - self.momentum).add_(
-                            mean, alpha=self.momentum)
-                        self.running_var.mul_(1 - self.momentum).add_(
-                            unbiased, alpha=self.momentum)
+                update_running_stats(self.running_mean, self.running_var,
+                                     mean, var, x.numel() // x.size(1),
+                                     factor)
                 return _BN3dPreFn.apply(x, self.weight, self.bias,
                                         mean_rstd, self.relu)
             return _BN3dFn.apply(x, self.weight, self.bias,
                                  self.running_mean, self.running_var,
-                                 self.momentum, self.eps, self.relu)
+                                 factor, self.eps, self.relu)
         C = require_native()
         return C.bn3d_infer(x.to(torch.bfloat16), self.weight, self.bias,
                             self.running_mean, self.running_var, self.eps,
@@ -90,14 +112,7 @@ class _BN3dPreFn(torch.autograd.Function):
         ctx.in_dtype = x.dtype
         return y
 
-    @staticmethod
-    def backward(ctx, dy):
-        C = require_native()
-        xb, mean_rstd, gamma, beta = ctx.saved_tensors
-        dx, dgamma, dbeta = C.bn3d_bwd(dy.to(torch.bfloat16), xb, mean_rstd,
-                                       gamma, beta, ctx.relu)
-        return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
-                dbeta.to(beta.dtype), None, None)
+    backward = staticmethod(_bn3d_backward)
 
 
 class _BNAddReluFn(torch.autograd.Function):
@@ -108,17 +123,13 @@ class _BNAddReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, gamma, beta, running_mean, running_var,
-                momentum, eps):
+                factor, eps):
         C = require_native()
         xb = x.to(torch.bfloat16)
         rb = res.to(torch.bfloat16)
         y, mean, var, mean_rstd = C.bn3d_fwd_res(xb, rb, gamma, beta, eps)
-        if running_mean is not None:
-            with torch.no_grad():
-                n = xb.numel() // xb.size(1)
-                unbiased = var * (n / max(n - 1, 1))
-                running_mean.mul_(1 - momentum).add_(mean, alpha=momentum)
-                running_var.mul_(1 - momentum).add_(unbiased, alpha=momentum)
+        update_running_stats(running_mean, running_var, mean, var,
+                             xb.numel() // xb.size(1), factor)
         ctx.save_for_backward(xb, rb, mean_rstd, gamma, beta)
         ctx.in_dtype = x.dtype
         return y
@@ -138,13 +149,12 @@ def bn_add_relu(x, residual, bn):
     """relu(bn(x) + residual) fused on the HIP path (train mode);
     falls back to the composed ops elsewhere."""
     if x.is_cuda and native_available() and bn.training:
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
+        factor = bn_momentum_step(bn)
         if residual.dtype != torch.bfloat16:
             residual = residual.to(torch.bfloat16)
         return _BNAddReluFn.apply(x, residual, bn.weight, bn.bias,
                                   bn.running_mean, bn.running_var,
-                                  bn.momentum, bn.eps)
+                                  factor, bn.eps)
     y = bn(x)
     if y.dtype != residual.dtype:
         residual = residual.to(y.dtype)

@@ -17,24 +17,69 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import native_available, require_native
+from .bnorm import (OpsBatchNorm2d, OpsBatchNorm3d, bn_momentum_step,
+                    update_running_stats)
 
-# Cin<16 stride-1 forwards route through the CTILE=1 spatial instances
-# instead of the igemm fallback. DEFAULT ON since round 2: measured A/B on
-# MI355X (profiles/r2_scaffold_ab.md) — 43.79 vs 44.46 ms/step on the VBM
-# flagship. COINN_SPATIAL_CI1=0 restores the igemm routing.
-_SPATIAL_CI1 = os.environ.get('COINN_SPATIAL_CI1', '1') == '1'
-# Double-buffered CTILE=16 stride-1 forward instances — numerically
-# validated on hardware but measured FLAT on the flagship (44.59 vs 44.46
-# ms/step, profiles/r2_scaffold_ab.md): block-level overlap already hides
-# the staging at multi-block occupancy. Kept compiled behind the env flag.
-_SPATIAL_DB = os.environ.get('COINN_SPATIAL_DB', '0') == '1'
 # Double-buffered stride-1 wgrad: numerically validated, measured WORSE
 # (45.89 ms/step — LDS doubling costs co-residency more than intra-block
 # overlap buys). Kept compiled behind the env flag.
 _WGRAD_DB = os.environ.get('COINN_WGRAD_DB', '0') == '1'
-# BN-backward reduction inside the dgrad epilogue — measured worse on the
-# flagship (see _ConvBNFn.backward); kernels kept, off by default.
-_BNBWD_FUSE = os.environ.get('COINN_BNBWD_FUSE', '0') == '1'
+
+
+# ---- 3x3x3 routing: pure functions of (channels, H, W, stride) ------------
+# H, W are the INPUT plane of the conv being routed; the depth never
+# matters (one slab covers 3 depth planes at any D).
+
+def _out_plane(H, W, stride):
+    return (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+
+
+def route_fwd3d(cin, H, W, stride):
+    """'spatial' | 'spatial-ctile1' | 'igemm' for the plain forward.
+
+    Spatial tap-reuse pays when the channel tile fills and chunks are
+    dense; else the igemm kernel wins (profiled in tools/bench_conv).
+    Cin<16 stride-1 layers take the CTILE=1 single-channel instances
+    (43.79 vs 44.46 ms/step on the flagship, profiles/r2_scaffold_ab.md).
+    """
+    oh, ow = _out_plane(H, W, stride)
+    if ow % 8 != 0 or oh * ow < 64:
+        return 'igemm'
+    if cin >= 16:
+        return 'spatial'
+    return 'spatial-ctile1' if stride == 1 else 'igemm'
+
+
+def route_fused_fwd3d(cin, H, W, stride):
+    """'spatial' | 'igemm' for the normalize-on-load forward (the fused
+    instances exist at the default channel tile only)."""
+    oh, ow = _out_plane(H, W, stride)
+    if ow % 8 == 0 and cin >= 16 and oh * ow >= 64:
+        return 'spatial'
+    return 'igemm'
+
+
+def route_dgrad3d(cout, H, W, stride):
+    """'spatial' | 's2-spatial' | 'igemm' for the input gradient; H, W are
+    the conv INPUT (= dx) plane, cout the channels of grad_out."""
+    if stride == 1:
+        if W % 8 == 0 and cout >= 16 and H * W >= 64:
+            return 'spatial'
+    elif stride == 2:
+        # parity classes: each works on the half-resolution sub-grid
+        hsub, wsub = (H + 1) // 2, (W + 1) // 2
+        if wsub % 8 == 0 and cout >= 32 and hsub * wsub >= 128:
+            return 's2-spatial'
+    return 'igemm'
+
+
+def _dgrad3d(C, go, wb, in_shape, stride):
+    route = route_dgrad3d(go.size(1), in_shape[3], in_shape[4], stride)
+    if route == 'spatial':
+        return C.conv3d_dgrad_spatial(go, wb, in_shape)
+    if route == 's2-spatial':
+        return C.conv3d_dgrad_s2_spatial(go, wb, in_shape)
+    return C.conv3d_dgrad(go, wb, in_shape, stride)
 
 
 class _Conv3dFn(torch.autograd.Function):
@@ -43,22 +88,12 @@ class _Conv3dFn(torch.autograd.Function):
         C = require_native()
         xb = x.to(torch.bfloat16)
         wb = weight.to(torch.bfloat16)
-        # spatial tap-reuse pays when the channel tile fills and chunks
-        # are dense; else the igemm kernel wins (profiled in tools/bench_conv)
-        ow = (xb.size(4) + 2 - 3) // stride + 1
-        oh = (xb.size(3) + 2 - 3) // stride + 1
-        min_chunk = 64
-        ci_ok = xb.size(1) >= 16 or (_SPATIAL_CI1 and stride == 1)
-        if (ow % 8 == 0 and ci_ok and oh * ow >= min_chunk):
-            if xb.size(1) < 16:
-                ctile_opt = 1
-            elif _SPATIAL_DB and stride == 1:
-                ctile_opt = 16
-            else:
-                ctile_opt = 0
-            out = C.conv3d_fwd_spatial(xb, wb, stride, ctile_opt)
-        else:
+        route = route_fwd3d(xb.size(1), xb.size(3), xb.size(4), stride)
+        if route == 'igemm':
             out = C.conv3d_fwd(xb, wb, stride)
+        else:
+            out = C.conv3d_fwd_spatial(xb, wb, stride,
+                                       1 if route == 'spatial-ctile1' else 0)
         if bias is not None:
             out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
         ctx.save_for_backward(xb, wb)
@@ -75,20 +110,8 @@ class _Conv3dFn(torch.autograd.Function):
         go = grad_out.to(torch.bfloat16).contiguous()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            wsub = (xb.size(4) + 1) // 2
-            hsub = (xb.size(3) + 1) // 2
-            if (ctx.stride == 1 and xb.size(4) % 8 == 0
-                    and go.size(1) >= 16
-                    and xb.size(3) * xb.size(4) >= 64):
-                gx = C.conv3d_dgrad_spatial(go, wb,
-                                            list(xb.shape)).to(ctx.in_dtype)
-            elif (ctx.stride == 2 and wsub % 8 == 0 and go.size(1) >= 32
-                    and hsub * wsub >= 128):
-                gx = C.conv3d_dgrad_s2_spatial(
-                    go, wb, list(xb.shape)).to(ctx.in_dtype)
-            else:
-                gx = C.conv3d_dgrad(go, wb, list(xb.shape),
-                                    ctx.stride).to(ctx.in_dtype)
+            gx = _dgrad3d(C, go, wb, list(xb.shape),
+                          ctx.stride).to(ctx.in_dtype)
         if ctx.needs_input_grad[1]:
             variant = 1 if (_WGRAD_DB and ctx.stride == 1) else 0
             gw = C.conv3d_wgrad(xb, go, ctx.stride,
@@ -119,10 +142,9 @@ class _ConvBNFn(torch.autograd.Function):
             a = gamma.float() * mean_rstd[:, 1]
             b = beta.float() - mean_rstd[:, 0] * a
             ab = torch.stack([a, b], 1).contiguous()
-        ow = (xb.size(4) + 2 - 3) // stride + 1
-        oh = (xb.size(3) + 2 - 3) // stride + 1
         stats = None
-        if ow % 8 == 0 and xb.size(1) >= 16 and oh * ow >= 64:
+        if route_fused_fwd3d(xb.size(1), xb.size(3), xb.size(4),
+                             stride) == 'spatial':
             if bias is None:
                 # epilogue also emits this output's BN statistics — the
                 # next fused pair skips its bn_reduce pass entirely
@@ -150,40 +172,14 @@ class _ConvBNFn(torch.autograd.Function):
         go = grad_out.to(torch.bfloat16).contiguous()
         stride = ctx.stride
         # dz = conv dgrad wrt the (virtual) normalized input — same
-        # routing as the unfused path. The stride-1 spatial dgrad ALSO
-        # folds the BN-backward reduction into its epilogue, so
-        # bn3d_bwd's standalone reduce pass disappears.
-        wsub = (xb.size(4) + 1) // 2
-        hsub = (xb.size(3) + 1) // 2
-        sums = None
-        if (_BNBWD_FUSE and stride == 1 and xb.size(4) % 8 == 0
-                and go.size(1) >= 16 and xb.size(3) * xb.size(4) >= 64):
-            # MEASURED WORSE by ~0.5 ms/step on the flagship (r2): the
-            # epilogue x_raw gathers slow the dgrad more than the removed
-            # reduce pass saves — off by default, COINN_BNBWD_FUSE=1
-            prm = torch.stack([mean_rstd[:, 0], mean_rstd[:, 1],
-                               gamma.float(), beta.float()], 1).contiguous()
-            dz, bsums = C.conv3d_dgrad_spatial_bnbwd(
-                go, wb, list(xb.shape), xb, prm)
-            sums = bsums.sum(0)
-        elif (stride == 1 and xb.size(4) % 8 == 0 and go.size(1) >= 16
-                and xb.size(3) * xb.size(4) >= 64):
-            dz = C.conv3d_dgrad_spatial(go, wb, list(xb.shape))
-        elif (stride == 2 and wsub % 8 == 0 and go.size(1) >= 32
-                and hsub * wsub >= 128):
-            dz = C.conv3d_dgrad_s2_spatial(go, wb, list(xb.shape))
-        else:
-            dz = C.conv3d_dgrad(go, wb, list(xb.shape), stride)
+        # routing as the unfused path; bn3d_bwd then runs its own reduce
+        # (folding it into the dgrad epilogue lost, docs/KERNELS.md)
+        dz = _dgrad3d(C, go, wb, list(xb.shape), stride)
         gw = C.conv3d_wgrad(xb, go, stride, 0, ab).to(ctx.w_dtype) \
             if ctx.needs_input_grad[4] else None
         gb = C.channel_sum(go) if (ctx.has_bias
                                    and ctx.needs_input_grad[5]) else None
-        if sums is not None:
-            dx, dgamma, dbeta = C.bn3d_bwd_pre(dz, xb, mean_rstd, gamma,
-                                               beta, True, sums)
-        else:
-            dx, dgamma, dbeta = C.bn3d_bwd(dz, xb, mean_rstd, gamma, beta,
-                                           True)
+        dx, dgamma, dbeta = C.bn3d_bwd(dz, xb, mean_rstd, gamma, beta, True)
         return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
                 dbeta.to(beta.dtype), None, gw, gb, None)
 
@@ -195,31 +191,29 @@ def conv_bn3d(x_raw, bn, conv):
     the 3x3x3/pad-1/stride-{1,2} family. Handles running-stat updates with
     the exact semantics of the unfused module.
     """
-    C = require_native()
-    xb = x_raw if x_raw.dtype == torch.bfloat16 \
-        else x_raw.to(torch.bfloat16)
-    if bn.training:
-        mean, var, mean_rstd = bn_stats_of(xb, bn.eps)
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-        if bn.running_mean is not None:
-            with torch.no_grad():
-                n = xb.numel() // xb.size(1)
-                unbiased = var * (n / max(n - 1, 1))
-                bn.running_mean.mul_(1 - bn.momentum).add_(
-                    mean, alpha=bn.momentum)
-                bn.running_var.mul_(1 - bn.momentum).add_(
-                    unbiased, alpha=bn.momentum)
-    else:
-        mean = bn.running_mean.float()
-        rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-        mean_rstd = torch.stack([mean, rstd], 1).contiguous()
-    out, stats = _ConvBNFn.apply(x_raw, bn.weight, bn.bias, mean_rstd,
+    out, stats = _ConvBNFn.apply(x_raw, bn.weight, bn.bias,
+                                 _bn_mean_rstd(x_raw, bn),
                                  conv.weight, conv.bias,
                                  int(conv.stride[0]))
     if stats.numel() > 0:
         out._coinn_bn_stats = stats
     return out
+
+
+def _bn_mean_rstd(x_raw, bn):
+    """[C][2] (mean, rstd) that `bn` normalizes x_raw with — batch stats
+    in training (running stats updated exactly as the unfused module
+    would), running stats in eval."""
+    xb = x_raw if x_raw.dtype == torch.bfloat16 \
+        else x_raw.to(torch.bfloat16)
+    if bn.training:
+        mean, var, mean_rstd = bn_stats_of(xb, bn.eps)
+        update_running_stats(bn.running_mean, bn.running_var, mean, var,
+                             xb.numel() // xb.size(1), bn_momentum_step(bn))
+        return mean_rstd
+    mean = bn.running_mean.float()
+    rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+    return torch.stack([mean, rstd], 1).contiguous()
 
 
 def bn_stats_of(xb, eps):
@@ -273,53 +267,35 @@ class _ConvBN2dFn(torch.autograd.Function):
 
 def conv_bn2d(x_raw, bn, conv):
     """Fused BN(+ReLU) -> 3x3 Conv2d (the 2D twin of conv_bn3d)."""
-    C = require_native()
-    xb = x_raw if x_raw.dtype == torch.bfloat16 \
-        else x_raw.to(torch.bfloat16)
-    if bn.training:
-        mean, var, mean_rstd = bn_stats_of(xb, bn.eps)
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-        if bn.running_mean is not None:
-            with torch.no_grad():
-                n = xb.numel() // xb.size(1)
-                unbiased = var * (n / max(n - 1, 1))
-                bn.running_mean.mul_(1 - bn.momentum).add_(
-                    mean, alpha=bn.momentum)
-                bn.running_var.mul_(1 - bn.momentum).add_(
-                    unbiased, alpha=bn.momentum)
-    else:
-        mean = bn.running_mean.float()
-        rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-        mean_rstd = torch.stack([mean, rstd], 1).contiguous()
-    return _ConvBN2dFn.apply(x_raw, bn.weight, bn.bias, mean_rstd,
+    return _ConvBN2dFn.apply(x_raw, bn.weight, bn.bias,
+                             _bn_mean_rstd(x_raw, bn),
                              conv.weight, int(conv.stride[0]))
+
+
+def _is_3x3_family(conv):
+    """3x3(x3) / pad 1 / isotropic stride 1 or 2 / no dilation / groups 1:
+    the family the in-tree implicit-GEMM kernels cover, at either rank."""
+    rank = len(conv.kernel_size)
+    return (conv.kernel_size == (3,) * rank
+            and conv.padding == (1,) * rank
+            and conv.stride[0] in (1, 2)
+            and conv.stride == (conv.stride[0],) * rank
+            and conv.dilation == (1,) * rank and conv.groups == 1)
 
 
 def can_fuse_bn_conv2d(bn, conv, x):
     """True when the 2D (bn -> conv) pair routes onto the fused kernels."""
-    from .bnorm import OpsBatchNorm2d
     return (x.is_cuda and native_available()
             and isinstance(bn, OpsBatchNorm2d) and bn.relu
             and isinstance(conv, OpsConv2d) and conv.bias is None
-            and conv.kernel_size == (3, 3)
-            and conv.padding == (1, 1)
-            and conv.stride[0] in (1, 2)
-            and conv.stride[0] == conv.stride[1]
-            and conv.dilation == (1, 1) and conv.groups == 1)
+            and _is_3x3_family(conv))
 
 
 def can_fuse_bn_conv(bn, conv, x):
     """True when the (bn -> conv) pair routes onto the fused kernels."""
-    from .bnorm import OpsBatchNorm3d
     return (x.is_cuda and native_available()
             and isinstance(bn, OpsBatchNorm3d) and bn.relu
-            and isinstance(conv, OpsConv3d)
-            and conv.kernel_size == (3, 3, 3)
-            and conv.padding == (1, 1, 1)
-            and conv.stride[0] in (1, 2)
-            and conv.stride[0] == conv.stride[1] == conv.stride[2]
-            and conv.dilation == (1, 1, 1) and conv.groups == 1)
+            and isinstance(conv, OpsConv3d) and _is_3x3_family(conv))
 
 
 class _ConvPw3dFn(torch.autograd.Function):
@@ -415,9 +391,7 @@ class OpsConv2d(nn.Conv2d):
     def forward(self, x):
         if x.is_cuda and native_available() and self.dilation == (1, 1) \
                 and self.groups == 1:
-            if (self.kernel_size == (3, 3) and self.padding == (1, 1)
-                    and self.stride[0] in (1, 2)
-                    and self.stride[0] == self.stride[1]):
+            if _is_3x3_family(self):
                 return _Conv2dFn.apply(x, self.weight, self.bias,
                                        int(self.stride[0]))
             # 7x7 stem: fwd+wgrad in-tree; input must not need a gradient
@@ -446,12 +420,7 @@ class OpsConv3d(nn.Conv3d):
     """
 
     def forward(self, x):
-        if (x.is_cuda and native_available()
-                and self.kernel_size == (3, 3, 3)
-                and self.padding == (1, 1, 1)
-                and self.stride[0] in (1, 2)
-                and self.stride[0] == self.stride[1] == self.stride[2]
-                and self.dilation == (1, 1, 1) and self.groups == 1):
+        if x.is_cuda and native_available() and _is_3x3_family(self):
             return _Conv3dFn.apply(x, self.weight, self.bias,
                                    int(self.stride[0]))
         if (x.is_cuda and native_available()

@@ -9,6 +9,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <type_traits>
+
 // torch.cuda's current stream (torch-on-ROCm tracks streams under the
 // masqueraded CUDA device type).
 static inline hipStream_t current_stream() {
@@ -25,6 +27,18 @@ static inline int elem_grid(int64_t n, int per_thread = 4) {
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
+}
+
+// Runtime value -> compile-time constant for the kernel-instance
+// dispatchers: f receives a std::integral_constant it can read with
+// decltype(c)::value as a template argument.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+template <class F>
+static inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 #define CHECK_GPU(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")

@@ -1185,6 +1185,15 @@ torch::Tensor conv3d_dgrad(torch::Tensor go, torch::Tensor w,
   return dx;
 }
 
+// (OWT, CHUNK) tilings of the conv3d_wgrad_s1[_db]_kernel instances: f(IntC<OWT>, IntC<CHUNK>)
+template <class F>
+static void dispatch_wgrad_tile(int owt, int chunk, F&& f) {
+  if (chunk == 64) f(IntC<8>{}, IntC<64>{});
+  else if (owt == 32) f(IntC<32>{}, IntC<128>{});
+  else if (owt == 16) f(IntC<16>{}, IntC<128>{});
+  else f(IntC<8>{}, IntC<128>{});
+}
+
 torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
                            int64_t stride, int64_t variant,
                            c10::optional<torch::Tensor> bn_ab_opt) {
@@ -1265,84 +1274,39 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
       outp = part.data_ptr<float>();
     }
     dim3 grid(co_t, ci_t, (unsigned)zstride);
-    auto L = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(),
-                         reinterpret_cast<const __bf16*>(xc.data_ptr()),
-                         reinterpret_cast<const __bf16*>(g.data_ptr()),
-                         outp, cd, nchunks, zstride, abp);
-    };
-    if (sliced) {
-      if (fuse) {
-        if (stride == 1) {
-          if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 1, 64, true, true>);
-          else if (OWT == 32)
-            L(conv3d_wgrad_s1_kernel<32, 1, 128, true, true>);
-          else if (OWT == 16)
-            L(conv3d_wgrad_s1_kernel<16, 1, 128, true, true>);
-          else L(conv3d_wgrad_s1_kernel<8, 1, 128, true, true>);
-        } else {
-          if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 2, 64, true, true>);
-          else if (OWT == 32)
-            L(conv3d_wgrad_s1_kernel<32, 2, 128, true, true>);
-          else if (OWT == 16)
-            L(conv3d_wgrad_s1_kernel<16, 2, 128, true, true>);
-          else L(conv3d_wgrad_s1_kernel<8, 2, 128, true, true>);
-        }
-      } else if (stride == 1) {
-        if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 1, 64, false, true>);
-        else if (OWT == 32)
-          L(conv3d_wgrad_s1_kernel<32, 1, 128, false, true>);
-        else if (OWT == 16)
-          L(conv3d_wgrad_s1_kernel<16, 1, 128, false, true>);
-        else L(conv3d_wgrad_s1_kernel<8, 1, 128, false, true>);
-      } else {
-        if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 2, 64, false, true>);
-        else if (OWT == 32)
-          L(conv3d_wgrad_s1_kernel<32, 2, 128, false, true>);
-        else if (OWT == 16)
-          L(conv3d_wgrad_s1_kernel<16, 2, 128, false, true>);
-        else L(conv3d_wgrad_s1_kernel<8, 2, 128, false, true>);
-      }
-      auto dwsum = part.sum(0);
-      return dwsum.view({cd.Cout, cd.Cin, 3, 3, 3});
-    }
-    if (fuse) {
-      if (stride == 1) {
-        if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 1, 64, true>);
-        else if (OWT == 32) L(conv3d_wgrad_s1_kernel<32, 1, 128, true>);
-        else if (OWT == 16) L(conv3d_wgrad_s1_kernel<16, 1, 128, true>);
-        else L(conv3d_wgrad_s1_kernel<8, 1, 128, true>);
-      } else {
-        if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 2, 64, true>);
-        else if (OWT == 32) L(conv3d_wgrad_s1_kernel<32, 2, 128, true>);
-        else if (OWT == 16) L(conv3d_wgrad_s1_kernel<16, 2, 128, true>);
-        else L(conv3d_wgrad_s1_kernel<8, 2, 128, true>);
-      }
+    if (stride == 1 && variant == 1) {
+      // experimental double-buffered instances (never fused or sliced)
+      dispatch_wgrad_tile(OWT, chunk, [&](auto owt, auto ch) {
+        hipLaunchKernelGGL(
+            (conv3d_wgrad_s1_db_kernel<decltype(owt)::value, 1,
+                                       decltype(ch)::value>),
+            grid, dim3(256), 0, current_stream(),
+            reinterpret_cast<const __bf16*>(xc.data_ptr()),
+            reinterpret_cast<const __bf16*>(g.data_ptr()),
+            dw.data_ptr<float>(), cd, nchunks, zstride);
+      });
       return dw.view({cd.Cout, cd.Cin, 3, 3, 3});
     }
-    auto LDB = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(),
-                         reinterpret_cast<const __bf16*>(xc.data_ptr()),
-                         reinterpret_cast<const __bf16*>(g.data_ptr()),
-                         dw.data_ptr<float>(), cd, nchunks, zstride);
-    };
-    if (stride == 1 && variant == 1) {
-      // experimental double-buffered instances
-      if (chunk == 64) LDB(conv3d_wgrad_s1_db_kernel<8, 1, 64>);
-      else if (OWT == 32) LDB(conv3d_wgrad_s1_db_kernel<32, 1>);
-      else if (OWT == 16) LDB(conv3d_wgrad_s1_db_kernel<16, 1>);
-      else LDB(conv3d_wgrad_s1_db_kernel<8, 1>);
-    } else if (stride == 1) {
-      if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 1, 64>);
-      else if (OWT == 32) L(conv3d_wgrad_s1_kernel<32, 1>);
-      else if (OWT == 16) L(conv3d_wgrad_s1_kernel<16, 1>);
-      else L(conv3d_wgrad_s1_kernel<8, 1>);
-    } else {
-      if (chunk == 64) L(conv3d_wgrad_s1_kernel<8, 2, 64>);
-      else if (OWT == 32) L(conv3d_wgrad_s1_kernel<32, 2>);
-      else if (OWT == 16) L(conv3d_wgrad_s1_kernel<16, 2>);
-      else L(conv3d_wgrad_s1_kernel<8, 2>);
-    }
+    // the whole instance family: tiling x stride x fused-BN x sliced
+    dispatch_wgrad_tile(OWT, chunk, [&](auto owt, auto ch) {
+      dispatch_bool(stride == 2, [&](auto s2) {
+        dispatch_bool(fuse, [&](auto fz) {
+          dispatch_bool(sliced, [&](auto sl) {
+            hipLaunchKernelGGL(
+                (conv3d_wgrad_s1_kernel<decltype(owt)::value,
+                                        decltype(s2)::value ? 2 : 1,
+                                        decltype(ch)::value,
+                                        decltype(fz)::value,
+                                        decltype(sl)::value>),
+                grid, dim3(256), 0, current_stream(),
+                reinterpret_cast<const __bf16*>(xc.data_ptr()),
+                reinterpret_cast<const __bf16*>(g.data_ptr()), outp, cd,
+                nchunks, zstride, abp);
+          });
+        });
+      });
+    });
+    if (sliced) dw = part.sum(0);
     return dw.view({cd.Cout, cd.Cin, 3, 3, 3});
   }
 

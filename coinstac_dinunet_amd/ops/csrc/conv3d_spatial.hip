@@ -41,11 +41,6 @@ struct SpDims {
 // SMODE 1: the epilogue also folds per-output-channel (sum, sumsq) of
 // the written elements into stats[hash_slice][NCOL][2] — the NEXT
 // block's BN statistics come for free (no standalone bn_reduce pass).
-// SMODE 2 (dgrad use): the written elements are dz of a BN(+ReLU)
-// output; fold the BN-BACKWARD reduction (sum(dz*mask), sum(dz*xhat*
-// mask)) instead, reading x_raw at the same offsets with the mask
-// recomputed from bn_prm = [mean, rstd, gamma, beta] per channel —
-// replaces the standalone bn_bwd_reduce pass.
 // Hash slices (blockIdx.x & 63) spread the atomics.
 template <int OWT, int STRIDE, int CTILE,
           int CHUNK = (STRIDE == 1 ? 256 : 128), bool FUSE_BN = false,
@@ -54,9 +49,7 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
     const __bf16* __restrict__ in, const __bf16* __restrict__ wb,
     __bf16* __restrict__ out, SpDims sd, int64_t nchunks,
     const float* __restrict__ bn_ab = nullptr,
-    float* __restrict__ stats = nullptr,
-    const __bf16* __restrict__ xraw = nullptr,
-    const float* __restrict__ bn_prm = nullptr) {
+    float* __restrict__ stats = nullptr) {
   constexpr int OHT = CHUNK / OWT;
   constexpr int IW = STRIDE * OWT;                  // staged interior width
   constexpr int W2 = IW + (STRIDE == 1 ? 4 : 2);
@@ -200,13 +193,6 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
     for (int j = 0; j < NCF; ++j) {
       const int col = ncol0 + j * 16 + ccol;
       if (col >= sd.NCOL) continue;
-      float p_mean = 0.f, p_rstd = 0.f, p_g = 0.f, p_b = 0.f;
-      if (SMODE == 2) {
-        p_mean = bn_prm[col * 4 + 0];
-        p_rstd = bn_prm[col * 4 + 1];
-        p_g = bn_prm[col * 4 + 2];
-        p_b = bn_prm[col * 4 + 3];
-      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = (wave * MPW + i) * 16 + crow0 + r;
@@ -223,13 +209,6 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
             const float vb = (float)(__bf16)v;
             cs[j] += vb;
             css[j] += vb * vb;
-          } else if (SMODE == 2) {
-            const float xh = ((float)xraw[off] - p_mean) * p_rstd;
-            if (p_g * xh + p_b > 0.f) {  // ReLU mask
-              const float d = (float)(__bf16)v;
-              cs[j] += d;
-              css[j] += d * xh;
-            }
           }
         }
       }
@@ -272,173 +251,78 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------
-// Double-buffered variant (experimental; routed only via ctile_opt=16):
-// stage slab kt+1 into the spare LDS buffer while the 14 k-steps of slab
-// kt run, one barrier per channel tile instead of two. CTILE=16 so two
-// buffers fit LDS. Same math, same WB layout (KT_PAD blocks at ctile 16).
-// ---------------------------------------------------------------------------
-template <int OWT, int STRIDE, int CTILE,
-          int CHUNK = (STRIDE == 1 ? 256 : 128)>
-__global__ __launch_bounds__(256) void conv3d_spatial_db_kernel(
-    const __bf16* __restrict__ in, const __bf16* __restrict__ wb,
-    __bf16* __restrict__ out, SpDims sd, int64_t nchunks) {
-  constexpr int NCF = 2;  // fixed 32-col tiles in the DB variant
-  constexpr int OHT = CHUNK / OWT;
-  constexpr int IW = STRIDE * OWT;
-  constexpr int W2 = IW + (STRIDE == 1 ? 4 : 2);
-  constexpr int H2 = STRIDE * (OHT - 1) + 3;
-  constexpr int MPW = CHUNK / 64;
-  static_assert(MPW >= 1, "chunk too small");
-  constexpr int KT_PAD = ((CTILE * 27 + 31) / 32) * 32;
-  __shared__ __bf16 sX[2][CTILE][3][H2][W2];
-  __shared__ unsigned short sKtab[KT_PAD + 8];
-
-  const int ncol0 = blockIdx.y * 32;
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int row = lane & 15, kg = lane >> 4;
-
-  const int wtiles = (sd.TW + OWT - 1) / OWT;
-  const int htiles = (sd.TH + OHT - 1) / OHT;
-
-  int64_t t = blockIdx.x;
-  const int wt = (int)(t % wtiles);
-  t /= wtiles;
-  const int ht = (int)(t % htiles);
-  t /= htiles;
-  const int td = (int)(t % sd.TD);
-  const int n = (int)(t / sd.TD);
-  const int oh0 = ht * OHT, ow0 = wt * OWT;
-
-  for (int k = tid; k < KT_PAD; k += 256) {
-    unsigned short off = 0;
-    if (k < CTILE * 27) {
-      const int cl = k / 27;
-      const int r27 = k - cl * 27;
-      const int a = r27 / 9, b = (r27 / 3) % 3, c = r27 % 3;
-      off = (unsigned short)(((cl * 3 + a) * H2 + b) * W2 + c);
-    }
-    sKtab[k] = off;
-  }
-
-  f32x4 acc[MPW][NCF];
-#pragma unroll
-  for (int i = 0; i < MPW; ++i)
-#pragma unroll
-    for (int j = 0; j < NCF; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  const int64_t HW = (int64_t)sd.H * sd.W;
-  const int64_t in_n = (int64_t)n * sd.KCH * sd.D * HW;
-  const int kts = (sd.KCH + CTILE - 1) / CTILE;
-
-  auto stage = [&](int kt, int buf) {
-    constexpr int NROWS = CTILE * 3 * H2;
-    for (int r = tid; r < NROWS; r += 256) {
-      const int hrow = r % H2;
-      const int a = (r / H2) % 3;
-      const int c = r / (3 * H2);
-      const int id = STRIDE * td - 1 + a;
-      const int ih = STRIDE * oh0 - 1 + hrow;
-      const int ch = kt * CTILE + c;
-      __bf16* dst = &sX[buf][c][a][hrow][0];
-      const bool row_ok = (unsigned)id < (unsigned)sd.D &&
-                          (unsigned)ih < (unsigned)sd.H && ch < sd.KCH;
-      if (!row_ok) {
-#pragma unroll
-        for (int col = 0; col < W2; ++col) dst[col] = (__bf16)0.f;
-        continue;
-      }
-      const __bf16* src = in + in_n + ((int64_t)ch * sd.D + id) * HW +
-                          (int64_t)ih * sd.W;
-      const int iw0 = STRIDE * ow0;
-      dst[0] = (iw0 > 0) ? src[iw0 - 1] : (__bf16)0.f;
-#pragma unroll
-      for (int v = 0; v < IW / 8; ++v) {
-        bf16x8 vec = *reinterpret_cast<const bf16x8*>(src + iw0 + v * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dst[1 + v * 8 + j] = vec[j];
-      }
-#pragma unroll
-      for (int e = 0; e < W2 - IW - 1; ++e) {
-        const int iw = iw0 + IW + e;
-        dst[1 + IW + e] = (iw < sd.W) ? src[iw] : (__bf16)0.f;
-      }
-    }
-  };
-
-  auto compute = [&](int kt, int buf) {
-    const int kbase_g = kt * KT_PAD;
-    const __bf16* slab = &sX[buf][0][0][0][0];
-#pragma unroll 1
-    for (int ks = 0; ks < KT_PAD / 32; ++ks) {
-      bf16x8 afrag[MPW];
-      {
-        const int kb = ks * 32 + kg * 8;
-        const u16x8 kt8 = *reinterpret_cast<const u16x8*>(&sKtab[kb]);
-#pragma unroll
-        for (int i = 0; i < MPW; ++i) {
-          const int m = (wave * MPW + i) * 16 + row;
-          const int base = (STRIDE * (m / OWT)) * W2 + STRIDE * (m % OWT);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            afrag[i][j] = slab[base + kt8[j]];
-        }
-      }
-      bf16x8 bfrag[NCF];
-#pragma unroll
-      for (int i = 0; i < NCF; ++i) {
-        const int col = ncol0 + i * 16 + row;
-        const int64_t off =
-            (int64_t)col * sd.Kpad + kbase_g + ks * 32 + kg * 8;
-        bfrag[i] = (col < sd.NCOL)
-                       ? *reinterpret_cast<const bf16x8*>(wb + off)
-                       : bf16x8{};
-      }
-#pragma unroll
-      for (int i = 0; i < MPW; ++i)
-#pragma unroll
-        for (int j = 0; j < NCF; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
-    }
-  };
-
-  stage(0, 0);
-  __syncthreads();
-  for (int kt = 0; kt < kts; ++kt) {
-    if (kt + 1 < kts) stage(kt + 1, (kt + 1) & 1);
-    compute(kt, kt & 1);
-    __syncthreads();  // next buffer staged AND this buffer's reads done
-  }
-
-  const int64_t THW = (int64_t)sd.TH * sd.TW;
-  const int64_t out_n = (int64_t)n * sd.NCOL * sd.TD * THW;
-  const int ccol = lane & 15;
-  const int crow0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < MPW; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = ncol0 + j * 16 + ccol;
-      if (col >= sd.NCOL) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = (wave * MPW + i) * 16 + crow0 + r;
-        const int oh = oh0 + m / OWT;
-        const int ow = ow0 + m % OWT;
-        if (oh < sd.TH && ow < sd.TW)
-          out[out_n + ((int64_t)col * sd.TD + td) * THW +
-              (int64_t)oh * sd.TW + ow] = (__bf16)(acc[i][j][r]);
-      }
-    }
-  }
+// ---- host -----------------------------------------------------------------
+static SpDims make_spdims(const torch::Tensor& in, int ncol, int td, int th,
+                          int tw) {
+  SpDims sd;
+  sd.N = (int)in.size(0); sd.KCH = (int)in.size(1);
+  sd.D = (int)in.size(2); sd.H = (int)in.size(3); sd.W = (int)in.size(4);
+  sd.NCOL = ncol;
+  sd.TD = td; sd.TH = th; sd.TW = tw;
+  sd.Kpad = 0;  // set once the weights are prepared
+  return sd;
 }
 
-// ---- host -----------------------------------------------------------------
+// What the caller wants from conv3d_spatial_kernel; which instance serves it
+// is plan_spatial's business.
+enum SpMode {
+  SP_PLAIN,        // forward
+  SP_CTILE1,       // forward, Cin < 16 (stride 1): single-channel tiles
+  SP_FUSED,        // forward with normalize-on-load
+  SP_FUSED_STATS,  // ... and the epilogue BN statistics
+  SP_DGRAD,        // stride-1 input gradient (go in, tap-flipped weights)
+};
+
+struct SpatialPlan {
+  int owt, chunk, ctile, ncolt;  // template arguments of the instance
+  int gcolt;                     // column tile the grid's y extent is cut by
+};
+
+static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
+  SpatialPlan p;
+  p.owt = sd.TW % 32 == 0 ? 32 : (sd.TW % 16 == 0 ? 16 : 8);
+  p.chunk = stride == 1 ? 256 : 128;
+  p.ctile = mode == SP_CTILE1 ? 1 : (stride == 1 ? 32 : 16);
+  p.ncolt = p.gcolt = 32;
+  const bool fused = mode == SP_FUSED || mode == SP_FUSED_STATS;
+  // thin-channel large-plane stride-1 layers (L2-class): chunk 512 at
+  // CTILE 16 doubles the m that amortizes each staged slab — dgrad 36.2 vs
+  // 36.6, fused-stats fwd 35.8 vs 36.1 ms/step on the flagship (r2)
+  if ((mode == SP_FUSED_STATS || mode == SP_DGRAD) && stride == 1 &&
+      sd.KCH <= 32 && sd.TW % 32 == 0 && sd.TH * sd.TW >= 512) {
+    p.chunk = 512;
+    p.ctile = 16;
+    return p;
+  }
+  // 64-col chunk-256 forward instances: halve the slab re-reads of the big
+  // stride-1 layers — 36.7 vs 37.5 ms/step on the flagship (r2)
+  if (stride == 1 && sd.NCOL >= 64 && (mode == SP_PLAIN || fused))
+    p.gcolt = 64;
+  // small images (d8-class): 64-position chunks keep the grid dense;
+  // wide-column instances halve the slab-staging redundancy there
+  // (PMC: 86% SQ_WAIT on the 32-col chunk-64 forms)
+  if (sd.TH * sd.TW < p.chunk) {
+    p.chunk = 64;
+    p.owt = 8;  // the chunk-64 instances are OWT=8
+    // swept on MI355X (r2): 128-col instances won at the deep layers
+    // (37.7 vs 38.2 ms/step flagship) — slab re-reads drop 4x vs 32-col
+    if (sd.NCOL >= 64 && mode != SP_CTILE1)
+      p.gcolt = sd.NCOL >= 128 ? 128 : 64;
+  }
+  p.ncolt = p.gcolt;
+  // KNOWN DEFECT, kept as it was (docs/NEXT.md, "Under-covered column
+  // grid"): the fused chunk-256 forwards and the dgrad have no wide
+  // instances and run the 32-column kernel on the grid cut for gcolt, so
+  // with NCOL >= 64 output columns past 32 of each gcolt are never written.
+  if (mode == SP_DGRAD || (fused && p.chunk == 256)) p.ncolt = 32;
+  return p;
+}
+
 // WB layout: [NCOL][kts * KT_PAD]; channel-tile block kt holds the CTILE*27
 // weights for channels [kt*CTILE, (kt+1)*CTILE), zero-padded to KT_PAD.
-static torch::Tensor prep_wb(torch::Tensor w_flat2d, int KCH, int ctile) {
+static torch::Tensor prep_wb(torch::Tensor w_flat2d, int KCH,
+                             const SpatialPlan& p) {
+  const int ctile = p.ctile;
   int ncol = (int)w_flat2d.size(0);
   int kt_pad = (ctile * 27 + 31) / 32 * 32;
   int kts = (KCH + ctile - 1) / ctile;
@@ -454,248 +338,150 @@ static torch::Tensor prep_wb(torch::Tensor w_flat2d, int KCH, int ctile) {
 
 static void launch_spatial(torch::Tensor in, torch::Tensor wb,
                            torch::Tensor out, SpDims sd, int stride,
-                           int ctile = 0, const float* bn_ab = nullptr,
+                           SpMode mode, const SpatialPlan& p,
+                           const float* bn_ab = nullptr,
                            float* stats = nullptr) {
-  int OWT = sd.TW % 32 == 0 ? 32 : (sd.TW % 16 == 0 ? 16 : 8);
-  int chunk = stride == 1 ? 256 : 128;
-  int ncolt = 32;
-  // 64-col chunk-256 main instances (non-fused path): halves the slab
-  // re-reads of the big stride-1 layers — measured 36.7 vs 37.5 ms/step
-  // on the flagship (r2); the fused-stats form stays 32-col (a wide
-  // variant of it mis-computed in an earlier build and is not needed:
-  // the fused fwd runs a different instance family).
-  if (stride == 1 && sd.NCOL >= 64 && ctile == 32) ncolt = 64;
-  // chunk-512/CTILE-16 instances for thin-channel stride-1 layers
-  // (L2-class): caller prepped wb with ctile=16 and passes ctile=165
-  const bool c512 = (ctile == 165);
-  // fused-stats wide form: numerically validated but measured SLOWER
-  // (37.3 vs 36.7 ms/step — the stats reduction on 4 col-fragments adds
-  // register pressure the fused fwd cannot afford); off by default.
-  const bool wide_fused = getenv("COINN_WIDE256F") != nullptr;
-  // small images (d8-class): 64-position chunks keep the grid dense;
-  // wide-column instances halve the slab-staging redundancy there
-  // (PMC: 86% SQ_WAIT on the 32-col chunk-64 forms)
-  if (sd.TH * sd.TW < chunk) {
-    chunk = 64;
-    OWT = 8;  // the chunk-64 instances are OWT=8
-    // swept on MI355X (r2): 128-col instances won at the deep layers
-    // (37.7 vs 38.2 ms/step flagship) — slab re-reads drop 4x vs 32-col
-    if (sd.NCOL >= 64 && ctile != 1) ncolt = sd.NCOL >= 128 ? 128 : 64;
-  }
-  int OHT = chunk / OWT;
-  int wtiles = (sd.TW + OWT - 1) / OWT;
-  int htiles = (sd.TH + OHT - 1) / OHT;
-  int64_t nchunks = (int64_t)sd.N * sd.TD * htiles * wtiles;
-  dim3 grid((unsigned)nchunks, (sd.NCOL + ncolt - 1) / ncolt);
+  const int oht = p.chunk / p.owt;
+  const int wtiles = (sd.TW + p.owt - 1) / p.owt;
+  const int htiles = (sd.TH + oht - 1) / oht;
+  const int64_t nchunks = (int64_t)sd.N * sd.TD * htiles * wtiles;
+  dim3 grid((unsigned)nchunks, (sd.NCOL + p.gcolt - 1) / p.gcolt);
   auto s = current_stream();
   const __bf16* ip = reinterpret_cast<const __bf16*>(in.data_ptr());
   const __bf16* wp = reinterpret_cast<const __bf16*>(wb.data_ptr());
   __bf16* op = reinterpret_cast<__bf16*>(out.data_ptr());
-  // db kernel has no bn_ab parameter; the regular kernel always takes one
-  // (hipLaunchKernelGGL cannot use default arguments)
-  auto LDB = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ip, wp, op, sd, nchunks);
+  // launches instance <OWT, STRIDE, CTILE, CHUNK, FUSE_BN, SMODE, NCOLT>
+  auto K = [&](auto owt, auto st, auto ct, auto ch, auto fz, auto sm,
+               auto nc) {
+    hipLaunchKernelGGL(
+        (conv3d_spatial_kernel<decltype(owt)::value, decltype(st)::value,
+                               decltype(ct)::value, decltype(ch)::value,
+                               decltype(fz)::value, decltype(sm)::value,
+                               decltype(nc)::value>),
+        grid, dim3(256), 0, s, ip, wp, op, sd, nchunks, bn_ab, stats);
   };
-  auto L = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ip, wp, op, sd, nchunks,
-                       (const float*)nullptr, (float*)nullptr,
-                       (const __bf16*)nullptr, (const float*)nullptr);
+  auto with_owt = [&](auto f) {
+    if (p.owt == 32) f(IntC<32>{});
+    else if (p.owt == 16) f(IntC<16>{});
+    else f(IntC<8>{});
   };
-  auto LF = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, ip, wp, op, sd, nchunks,
-                       bn_ab, stats, (const __bf16*)nullptr,
-                       (const float*)nullptr);
+  // f(FUSE_BN, SMODE) of the mode
+  auto with_epilogue = [&](auto f) {
+    if (mode == SP_FUSED_STATS) f(std::true_type{}, IntC<1>{});
+    else if (mode == SP_FUSED) f(std::true_type{}, IntC<0>{});
+    else f(std::false_type{}, IntC<0>{});
   };
-  if (bn_ab != nullptr && stats != nullptr) {
-    // fused normalize-on-load + epilogue-stats instances
-    if (c512 && stride == 1) {
-      int OHT5 = 512 / 32;
-      int ht5 = (sd.TH + OHT5 - 1) / OHT5;
-      int wt5 = (sd.TW + 31) / 32;
-      nchunks = (int64_t)sd.N * sd.TD * ht5 * wt5;
-      grid = dim3((unsigned)nchunks, (sd.NCOL + 31) / 32);
-      LF(conv3d_spatial_kernel<32, 1, 16, 512, true, 1>);
-      return;
-    }
-    if (stride == 1) {
-      if (chunk == 64 && ncolt == 128)
-        LF(conv3d_spatial_kernel<8, 1, 32, 64, true, 1, 128>);
-      else if (chunk == 64 && ncolt == 64)
-        LF(conv3d_spatial_kernel<8, 1, 32, 64, true, 1, 64>);
-      else if (chunk == 64) LF(conv3d_spatial_kernel<8, 1, 32, 64, true, 1>);
-      else if (OWT == 32 && wide_fused && ncolt == 64)
-        LF(conv3d_spatial_kernel<32, 1, 32, 256, true, 1, 64>);
-      else if (OWT == 32)
-        LF(conv3d_spatial_kernel<32, 1, 32, 256, true, 1>);
-      else if (OWT == 16 && wide_fused && ncolt == 64)
-        LF(conv3d_spatial_kernel<16, 1, 32, 256, true, 1, 64>);
-      else if (OWT == 16)
-        LF(conv3d_spatial_kernel<16, 1, 32, 256, true, 1>);
-      else LF(conv3d_spatial_kernel<8, 1, 32, 256, true, 1>);
-    } else {
-      if (chunk == 64 && ncolt == 128)
-        LF(conv3d_spatial_kernel<8, 2, 16, 64, true, 1, 128>);
-      else if (chunk == 64 && ncolt == 64)
-        LF(conv3d_spatial_kernel<8, 2, 16, 64, true, 1, 64>);
-      else if (chunk == 64) LF(conv3d_spatial_kernel<8, 2, 16, 64, true, 1>);
-      else if (OWT == 32)
-        LF(conv3d_spatial_kernel<32, 2, 16, 128, true, 1>);
-      else if (OWT == 16)
-        LF(conv3d_spatial_kernel<16, 2, 16, 128, true, 1>);
-      else LF(conv3d_spatial_kernel<8, 2, 16, 128, true, 1>);
-    }
-    return;
-  }
-  if (bn_ab != nullptr) {
-    // fused normalize-on-load instances (default tilings only)
-    if (stride == 1) {
-      if (chunk == 64 && ncolt == 128)
-        LF(conv3d_spatial_kernel<8, 1, 32, 64, true, 0, 128>);
-      else if (chunk == 64 && ncolt == 64)
-        LF(conv3d_spatial_kernel<8, 1, 32, 64, true, 0, 64>);
-      else if (chunk == 64) LF(conv3d_spatial_kernel<8, 1, 32, 64, true>);
-      else if (OWT == 32) LF(conv3d_spatial_kernel<32, 1, 32, 256, true>);
-      else if (OWT == 16) LF(conv3d_spatial_kernel<16, 1, 32, 256, true>);
-      else LF(conv3d_spatial_kernel<8, 1, 32, 256, true>);
-    } else {
-      if (chunk == 64 && ncolt == 128)
-        LF(conv3d_spatial_kernel<8, 2, 16, 64, true, 0, 128>);
-      else if (chunk == 64 && ncolt == 64)
-        LF(conv3d_spatial_kernel<8, 2, 16, 64, true, 0, 64>);
-      else if (chunk == 64) LF(conv3d_spatial_kernel<8, 2, 16, 64, true>);
-      else if (OWT == 32) LF(conv3d_spatial_kernel<32, 2, 16, 128, true>);
-      else if (OWT == 16) LF(conv3d_spatial_kernel<16, 2, 16, 128, true>);
-      else LF(conv3d_spatial_kernel<8, 2, 16, 128, true>);
-    }
-    return;
-  }
-  if (stride == 1 && chunk == 64 && ncolt == 128 && ctile == 32) {
-    L(conv3d_spatial_kernel<8, 1, 32, 64, false, 0, 128>);
-  } else if (stride == 2 && chunk == 64 && ncolt == 128) {
-    L(conv3d_spatial_kernel<8, 2, 16, 64, false, 0, 128>);
-  } else if (stride == 1 && chunk == 64 && ncolt == 64 && ctile == 32) {
-    L(conv3d_spatial_kernel<8, 1, 32, 64, false, 0, 64>);
-  } else if (stride == 2 && chunk == 64 && ncolt == 64) {
-    L(conv3d_spatial_kernel<8, 2, 16, 64, false, 0, 64>);
-  } else if (stride == 1 && ctile == 16) {
-    // experimental double-buffered CTILE=16 instances (ctile_opt=16)
-    if (chunk == 64) LDB(conv3d_spatial_db_kernel<8, 1, 16, 64>);
-    else if (OWT == 32) LDB(conv3d_spatial_db_kernel<32, 1, 16>);
-    else if (OWT == 16) LDB(conv3d_spatial_db_kernel<16, 1, 16>);
-    else LDB(conv3d_spatial_db_kernel<8, 1, 16>);
-  } else if (stride == 1 && ctile == 1) {
+  const std::false_type plain{};
+  if (p.ctile == 1) {
     // single-channel (first-layer) instances: one 32-k-step covers the
-    // whole 27-tap K, slab is [1][3][H2][W2]
-    if (chunk == 64) L(conv3d_spatial_kernel<8, 1, 1, 64>);
-    else if (OWT == 32) L(conv3d_spatial_kernel<32, 1, 1>);
-    else if (OWT == 16) L(conv3d_spatial_kernel<16, 1, 1>);
-    else L(conv3d_spatial_kernel<8, 1, 1>);
-  } else if (c512 && stride == 1) {
-    // grid must be recomputed for the larger chunk
-    {
-      int OHT5 = 512 / 32;
-      int ht5 = (sd.TH + OHT5 - 1) / OHT5;
-      int wt5 = (sd.TW + 31) / 32;
-      nchunks = (int64_t)sd.N * sd.TD * ht5 * wt5;
-      grid = dim3((unsigned)nchunks, (sd.NCOL + 31) / 32);
-    }
-    L(conv3d_spatial_kernel<32, 1, 16, 512>);
-  } else if (stride == 1 && ncolt == 64 && chunk == 256) {
-    if (OWT == 32) L(conv3d_spatial_kernel<32, 1, 32, 256, false, 0, 64>);
-    else if (OWT == 16)
-      L(conv3d_spatial_kernel<16, 1, 32, 256, false, 0, 64>);
-    else L(conv3d_spatial_kernel<8, 1, 32, 256, false, 0, 64>);
-  } else if (stride == 1) {
-    if (chunk == 64) L(conv3d_spatial_kernel<8, 1, 32, 64>);
-    else if (OWT == 32) L(conv3d_spatial_kernel<32, 1, 32>);
-    else if (OWT == 16) L(conv3d_spatial_kernel<16, 1, 32>);
-    else L(conv3d_spatial_kernel<8, 1, 32>);
+    // whole 27-tap K, slab is [1][3][H2][W2]; plain epilogue only
+    if (p.chunk == 64)
+      K(IntC<8>{}, IntC<1>{}, IntC<1>{}, IntC<64>{}, plain, IntC<0>{},
+        IntC<32>{});
+    else
+      with_owt([&](auto owt) {
+        K(owt, IntC<1>{}, IntC<1>{}, IntC<256>{}, plain, IntC<0>{},
+          IntC<32>{});
+      });
+  } else if (p.chunk == 512) {
+    // plain (dgrad) and fused+stats (fwd) only
+    dispatch_bool(mode == SP_FUSED_STATS, [&](auto fs) {
+      K(IntC<32>{}, IntC<1>{}, IntC<16>{}, IntC<512>{}, fs,
+        IntC<decltype(fs)::value ? 1 : 0>{}, IntC<32>{});
+    });
+  } else if (p.chunk == 64) {
+    // every epilogue x {32, 64, 128} columns x stride
+    with_epilogue([&](auto fz, auto sm) {
+      auto with_ncolt = [&](auto f) {
+        if (p.ncolt == 128) f(IntC<128>{});
+        else if (p.ncolt == 64) f(IntC<64>{});
+        else f(IntC<32>{});
+      };
+      with_ncolt([&](auto nc) {
+        if (stride == 1)
+          K(IntC<8>{}, IntC<1>{}, IntC<32>{}, IntC<64>{}, fz, sm, nc);
+        else
+          K(IntC<8>{}, IntC<2>{}, IntC<16>{}, IntC<64>{}, fz, sm, nc);
+      });
+    });
+  } else if (stride == 2) {
+    with_epilogue([&](auto fz, auto sm) {
+      with_owt([&](auto owt) {
+        K(owt, IntC<2>{}, IntC<16>{}, IntC<128>{}, fz, sm, IntC<32>{});
+      });
+    });
+  } else if (p.ncolt == 64) {
+    // wide chunk-256: plain forward only (the fused-stats wide form lost,
+    // docs/KERNELS.md)
+    with_owt([&](auto owt) {
+      K(owt, IntC<1>{}, IntC<32>{}, IntC<256>{}, plain, IntC<0>{},
+        IntC<64>{});
+    });
   } else {
-    if (chunk == 64) L(conv3d_spatial_kernel<8, 2, 16, 64>);
-    else if (OWT == 32) L(conv3d_spatial_kernel<32, 2, 16>);
-    else if (OWT == 16) L(conv3d_spatial_kernel<16, 2, 16>);
-    else L(conv3d_spatial_kernel<8, 2, 16>);
+    with_epilogue([&](auto fz, auto sm) {
+      with_owt([&](auto owt) {
+        K(owt, IntC<1>{}, IntC<32>{}, IntC<256>{}, fz, sm, IntC<32>{});
+      });
+    });
   }
 }
 
+// shared body of the two forward entry points: {out, stats-or-undefined}
+static std::vector<torch::Tensor> spatial_fwd(torch::Tensor x,
+                                              torch::Tensor w, int stride,
+                                              SpMode mode,
+                                              torch::Tensor bn_ab) {
+  CHECK_GPU(x);
+  auto xc = x.contiguous();
+  auto wc = w.to(torch::kBFloat16).contiguous();
+  TORCH_CHECK(xc.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(stride == 1 || stride == 2);
+  torch::Tensor ab, stats;
+  if (mode == SP_FUSED || mode == SP_FUSED_STATS) {
+    ab = bn_ab.to(torch::kFloat32).contiguous();
+    TORCH_CHECK(ab.numel() == 2 * x.size(1), "bn_ab must be [Cin,2]");
+  }
+  auto odim = [&](int i) { return ((int)xc.size(i) + 2 - 3) / stride + 1; };
+  SpDims sd = make_spdims(xc, (int)wc.size(0), odim(2), odim(3), odim(4));
+  const SpatialPlan plan = plan_spatial(sd, stride, mode);
+  auto wb = prep_wb(wc.reshape({sd.NCOL, (int64_t)sd.KCH * 27}), sd.KCH,
+                    plan);
+  sd.Kpad = (int)wb.size(1);
+  auto out = torch::empty({sd.N, sd.NCOL, sd.TD, sd.TH, sd.TW},
+                          xc.options());
+  // stats[64][Cout][2]: hash-sliced partial sums; callers fold with sum(0)
+  if (mode == SP_FUSED_STATS)
+    stats = torch::zeros({64, sd.NCOL, 2},
+                         xc.options().dtype(torch::kFloat32));
+  launch_spatial(xc, wb, out, sd, stride, mode, plan,
+                 ab.defined() ? ab.data_ptr<float>() : nullptr,
+                 stats.defined() ? stats.data_ptr<float>() : nullptr);
+  return {out, stats};
+}
+
+// ctile_opt: 0 = the default tiling; 1 = the CTILE=1 single-channel
+// instances (stride 1; ignored at stride 2).
 torch::Tensor conv3d_fwd_spatial(torch::Tensor x, torch::Tensor w,
                                  int64_t stride, int64_t ctile_opt,
                                  c10::optional<torch::Tensor> bn_ab_opt) {
   torch::Tensor bn_ab = bn_ab_opt.value_or(torch::Tensor());
-  CHECK_GPU(x);
-  auto xc = x.contiguous();
-  auto wc = w.to(torch::kBFloat16).contiguous();
-  TORCH_CHECK(xc.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(stride == 1 || stride == 2);
+  TORCH_CHECK(ctile_opt == 0 || ctile_opt == 1, "ctile_opt must be 0 or 1");
   const bool fuse = bn_ab.defined() && bn_ab.numel() > 0;
-  torch::Tensor ab;
-  if (fuse) {
-    TORCH_CHECK(ctile_opt == 0, "fused BN requires default tiling");
-    ab = bn_ab.to(torch::kFloat32).contiguous();
-    TORCH_CHECK(ab.numel() == 2 * x.size(1), "bn_ab must be [Cin,2]");
-  }
-  SpDims sd;
-  sd.N = (int)xc.size(0); sd.KCH = (int)xc.size(1);
-  sd.D = (int)xc.size(2); sd.H = (int)xc.size(3); sd.W = (int)xc.size(4);
-  sd.NCOL = (int)wc.size(0);
-  sd.TD = (sd.D + 2 - 3) / (int)stride + 1;
-  sd.TH = (sd.H + 2 - 3) / (int)stride + 1;
-  sd.TW = (sd.W + 2 - 3) / (int)stride + 1;
-  // ctile_opt=1 opts into the CTILE=1 single-channel instances;
-  // ctile_opt=16 into the double-buffered CTILE=16 instances
-  // (both stride 1 only); 0 = the default tiling.
-  int ctile = stride == 1
-                  ? ((ctile_opt == 1 || ctile_opt == 16) ? (int)ctile_opt : 32)
-                  : 16;
-  auto wb = prep_wb(wc.reshape({sd.NCOL, (int64_t)sd.KCH * 27}), sd.KCH,
-                    ctile);
-  sd.Kpad = (int)wb.size(1);
-  auto out = torch::empty({sd.N, sd.NCOL, sd.TD, sd.TH, sd.TW},
-                          xc.options());
-  launch_spatial(xc, wb, out, sd, (int)stride, ctile,
-                 fuse ? ab.data_ptr<float>() : nullptr);
-  return out;
+  TORCH_CHECK(!fuse || ctile_opt == 0, "fused BN requires default tiling");
+  const SpMode mode = fuse ? SP_FUSED
+                           : (ctile_opt == 1 && stride == 1 ? SP_CTILE1
+                                                            : SP_PLAIN);
+  return spatial_fwd(x, w, (int)stride, mode, bn_ab)[0];
 }
 
 // fused fwd + epilogue BN statistics: returns {out, stats[64][Cout][2]}
-// (hash-sliced partial sums; callers fold with stats.sum(0)).
 std::vector<torch::Tensor> conv3d_fwd_spatial_stats(
     torch::Tensor x, torch::Tensor w, int64_t stride,
     c10::optional<torch::Tensor> bn_ab_opt) {
   torch::Tensor bn_ab = bn_ab_opt.value_or(torch::Tensor());
-  CHECK_GPU(x);
-  auto xc = x.contiguous();
-  auto wc = w.to(torch::kBFloat16).contiguous();
-  TORCH_CHECK(xc.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(stride == 1 || stride == 2);
   TORCH_CHECK(bn_ab.defined() && bn_ab.numel() > 0,
               "stats form requires the fused-BN path");
-  auto ab = bn_ab.to(torch::kFloat32).contiguous();
-  SpDims sd;
-  sd.N = (int)xc.size(0); sd.KCH = (int)xc.size(1);
-  sd.D = (int)xc.size(2); sd.H = (int)xc.size(3); sd.W = (int)xc.size(4);
-  sd.NCOL = (int)wc.size(0);
-  sd.TD = (sd.D + 2 - 3) / (int)stride + 1;
-  sd.TH = (sd.H + 2 - 3) / (int)stride + 1;
-  sd.TW = (sd.W + 2 - 3) / (int)stride + 1;
-  int ctile = stride == 1 ? 32 : 16;
-  // chunk-512 thin-channel fused fwd: measured 35.8 vs 36.1 ms/step
-  // (r2); COINN_C512F=0 reverts
-  const char* c5e = getenv("COINN_C512F");
-  const bool c512 = (!c5e || c5e[0] != '0') && stride == 1 &&
-                    sd.KCH <= 32 && sd.TW % 32 == 0 &&
-                    sd.TH * sd.TW >= 512;
-  if (c512) ctile = 16;
-  auto wb = prep_wb(wc.reshape({sd.NCOL, (int64_t)sd.KCH * 27}), sd.KCH,
-                    ctile);
-  sd.Kpad = (int)wb.size(1);
-  auto out = torch::empty({sd.N, sd.NCOL, sd.TD, sd.TH, sd.TW},
-                          xc.options());
-  auto stats = torch::zeros({64, sd.NCOL, 2},
-                            xc.options().dtype(torch::kFloat32));
-  launch_spatial(xc, wb, out, sd, (int)stride, c512 ? 165 : ctile,
-                 ab.data_ptr<float>(), stats.data_ptr<float>());
-  return {out, stats};
+  return spatial_fwd(x, w, (int)stride, SP_FUSED_STATS, bn_ab);
 }
 
 torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
@@ -703,80 +489,17 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
   CHECK_GPU(go);
   auto g = go.to(torch::kBFloat16).contiguous();
   auto wc = w.to(torch::kBFloat16).contiguous();
-  SpDims sd;
-  sd.N = (int)g.size(0); sd.KCH = (int)g.size(1);
-  sd.D = (int)g.size(2); sd.H = (int)g.size(3); sd.W = (int)g.size(4);
-  sd.NCOL = (int)in_shape[1];
-  sd.TD = (int)in_shape[2]; sd.TH = (int)in_shape[3];
-  sd.TW = (int)in_shape[4];
+  SpDims sd = make_spdims(g, (int)in_shape[1], (int)in_shape[2],
+                          (int)in_shape[3], (int)in_shape[4]);
   int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
   auto wf = wc.reshape({Cout, Cin, 27}).flip(-1).permute({1, 0, 2})
                 .reshape({Cin, (int64_t)Cout * 27}).contiguous();
-  // thin-channel large-plane layers: the chunk-512/CTILE-16 instance
-  // doubles the m amortizing each staged slab (measured 36.2 vs 36.6
-  // ms/step on the flagship, r2; COINN_C512=0 reverts)
-  const char* c512_env = getenv("COINN_C512");
-  const bool c512 = (!c512_env || c512_env[0] != '0') && sd.KCH <= 32 &&
-                    sd.TW % 32 == 0 && sd.TH * sd.TW >= 512;
-  auto wb = prep_wb(wf, Cout, c512 ? 16 : 32);
+  const SpatialPlan plan = plan_spatial(sd, 1, SP_DGRAD);
+  auto wb = prep_wb(wf, Cout, plan);
   sd.Kpad = (int)wb.size(1);
   auto dx = torch::empty(in_shape, g.options());
-  launch_spatial(g, wb, dx, sd, 1, c512 ? 165 : 0);
+  launch_spatial(g, wb, dx, sd, 1, SP_DGRAD, plan);
   return dx;
-}
-
-// stride-1 dgrad that ALSO folds the BN-backward reduction of the dz it
-// writes: returns {dz, bsums[64][Cin][2]} with bsums = hash-sliced
-// partials of (sum dz*mask, sum dz*xhat*mask). bn_prm packs
-// [mean, rstd, gamma, beta] per channel of the BN being backpropped.
-std::vector<torch::Tensor> conv3d_dgrad_spatial_bnbwd(
-    torch::Tensor go, torch::Tensor w, std::vector<int64_t> in_shape,
-    torch::Tensor xraw, torch::Tensor bn_prm) {
-  CHECK_GPU(go);
-  auto g = go.to(torch::kBFloat16).contiguous();
-  auto wc = w.to(torch::kBFloat16).contiguous();
-  auto xr = xraw.contiguous();
-  TORCH_CHECK(xr.scalar_type() == torch::kBFloat16, "xraw must be bf16");
-  auto prm = bn_prm.to(torch::kFloat32).contiguous();
-  SpDims sd;
-  sd.N = (int)g.size(0); sd.KCH = (int)g.size(1);
-  sd.D = (int)g.size(2); sd.H = (int)g.size(3); sd.W = (int)g.size(4);
-  sd.NCOL = (int)in_shape[1];
-  sd.TD = (int)in_shape[2]; sd.TH = (int)in_shape[3];
-  sd.TW = (int)in_shape[4];
-  TORCH_CHECK(prm.numel() == 4 * sd.NCOL, "bn_prm must be [Cin,4]");
-  int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
-  auto wf = wc.reshape({Cout, Cin, 27}).flip(-1).permute({1, 0, 2})
-                .reshape({Cin, (int64_t)Cout * 27}).contiguous();
-  auto wb = prep_wb(wf, Cout, 32);
-  sd.Kpad = (int)wb.size(1);
-  auto dx = torch::empty(in_shape, g.options());
-  auto bsums = torch::zeros({64, sd.NCOL, 2},
-                            g.options().dtype(torch::kFloat32));
-
-  int OWT = sd.TW % 32 == 0 ? 32 : (sd.TW % 16 == 0 ? 16 : 8);
-  int chunk = 256;
-  if (sd.TH * sd.TW < chunk) { chunk = 64; OWT = 8; }
-  int OHT = chunk / OWT;
-  int wtiles = (sd.TW + OWT - 1) / OWT;
-  int htiles = (sd.TH + OHT - 1) / OHT;
-  int64_t nchunks = (int64_t)sd.N * sd.TD * htiles * wtiles;
-  dim3 grid((unsigned)nchunks, (sd.NCOL + 31) / 32);
-  auto st = current_stream();
-  auto LB = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st,
-                       reinterpret_cast<const __bf16*>(g.data_ptr()),
-                       reinterpret_cast<const __bf16*>(wb.data_ptr()),
-                       reinterpret_cast<__bf16*>(dx.data_ptr()), sd, nchunks,
-                       (const float*)nullptr, bsums.data_ptr<float>(),
-                       reinterpret_cast<const __bf16*>(xr.data_ptr()),
-                       prm.data_ptr<float>());
-  };
-  if (chunk == 64) LB(conv3d_spatial_kernel<8, 1, 32, 64, false, 2>);
-  else if (OWT == 32) LB(conv3d_spatial_kernel<32, 1, 32, 256, false, 2>);
-  else if (OWT == 16) LB(conv3d_spatial_kernel<16, 1, 32, 256, false, 2>);
-  else LB(conv3d_spatial_kernel<8, 1, 32, 256, false, 2>);
-  return {dx, bsums};
 }
 
 // ---------------------------------------------------------------------------
@@ -965,12 +688,8 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
   auto g = go.to(torch::kBFloat16).contiguous();
   auto wc = w.to(torch::kBFloat16).contiguous();
   int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
-  SpDims sd;
-  sd.N = (int)g.size(0); sd.KCH = Cout;
-  sd.D = (int)g.size(2); sd.H = (int)g.size(3); sd.W = (int)g.size(4);
-  sd.NCOL = Cin;
-  sd.TD = (int)in_shape[2]; sd.TH = (int)in_shape[3];
-  sd.TW = (int)in_shape[4];
+  SpDims sd = make_spdims(g, Cin, (int)in_shape[2], (int)in_shape[3],
+                          (int)in_shape[4]);
 
   // per-class tap-gathered weights: WBc[ci][co*T + r]. The tap index
   // tensors are compile-time constants — cached per device so no H2D

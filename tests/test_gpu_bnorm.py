@@ -69,3 +69,22 @@ def test_bn3d_module_running_stats(dev):
     y = m(x)
     yr = ref(x.float())
     torch.testing.assert_close(y.float(), yr, rtol=5e-2, atol=5e-2)
+
+
+def test_bn3d_module_cumulative_average_momentum_none(dev):
+    """momentum=None is nn.BatchNorm's cumulative moving average: the
+    update factor is 1/num_batches_tracked (it raised TypeError before)."""
+    torch.manual_seed(2)
+    m = OpsBatchNorm3d(8, momentum=None).to(dev)
+    ref = torch.nn.BatchNorm3d(8, momentum=None).to(dev)
+    m.train()
+    ref.train()
+    for _ in range(2):
+        x = (torch.randn(2, 8, 4, 8, 8, device=dev) * 2 + 1).bfloat16()
+        m(x)
+        ref(x.float())
+    assert int(m.num_batches_tracked) == int(ref.num_batches_tracked) == 2
+    torch.testing.assert_close(m.running_mean, ref.running_mean,
+                               rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(m.running_var, ref.running_var,
+                               rtol=2e-2, atol=5e-2)
