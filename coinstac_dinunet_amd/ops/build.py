@@ -26,6 +26,25 @@ def _newer(paths, target):
     return any(os.path.getmtime(p) > t for p in paths)
 
 
+def compile_flags():
+    """hipcc flags (arch, defines, include paths) every csrc file is
+    compiled with; tools/kernel_resources.py reuses them."""
+    includes = ce.include_paths() + [sysconfig.get_paths()['include']]
+    try:
+        import pybind11
+        includes.append(pybind11.get_include())
+    except ImportError:
+        pass
+    abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
+    return ([f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC',
+             '-D__HIP_PLATFORM_AMD__=1', '-DUSE_ROCM=1', '-DHIPBLAS_V2',
+             f'-D_GLIBCXX_USE_CXX11_ABI={abi}',
+             '-DTORCH_EXTENSION_NAME=_hip_ops',
+             '-DTORCH_API_INCLUDE_EXTENSION_H',
+             '-Wno-unused-result', '-Wno-deprecated-declarations']
+            + [f'-I{d}' for d in includes])
+
+
 def build(verbose=True, force=False):
     sources = sorted(
         os.path.join(CSRC, f) for f in os.listdir(CSRC)
@@ -35,22 +54,8 @@ def build(verbose=True, force=False):
     if not force and not _newer(sources + headers, OUT_SO):
         return OUT_SO
 
-    includes = ce.include_paths() + [sysconfig.get_paths()['include']]
-    try:
-        import pybind11
-        includes.append(pybind11.get_include())
-    except ImportError:
-        pass
     lib_dir = ce.library_paths()[0]
-
-    abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
-    cflags = ([f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC',
-               '-D__HIP_PLATFORM_AMD__=1', '-DUSE_ROCM=1', '-DHIPBLAS_V2',
-               f'-D_GLIBCXX_USE_CXX11_ABI={abi}',
-               '-DTORCH_EXTENSION_NAME=_hip_ops',
-               '-DTORCH_API_INCLUDE_EXTENSION_H',
-               '-Wno-unused-result', '-Wno-deprecated-declarations']
-              + [f'-I{d}' for d in includes])
+    cflags = compile_flags()
 
     objs = []
     build_dir = os.path.join(HERE, 'build')

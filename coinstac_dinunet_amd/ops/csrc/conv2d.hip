@@ -672,7 +672,7 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_sp_kernel(
   float* out = SLICED ? dw + (int64_t)blockIdx.z * cd.Cout * K : dw;
   const int ccol = lane & 15;
   const int crow0 = (lane >> 4) * 4;
-#pragma unroll 1
+#pragma unroll  // static acc index: the accumulators stay in registers
   for (int tp = 0; tp < 9; ++tp) {
 #pragma unroll
     for (int f = 0; f < CIF; ++f) {
@@ -1040,8 +1040,13 @@ torch::Tensor conv2d_wgrad(torch::Tensor x, torch::Tensor go,
   cd.OH = (int)g.size(2); cd.OW = (int)g.size(3);
   int K = cd.Cin * (int)(ks * ks);
   int64_t M = (int64_t)cd.N * cd.OH * cd.OW;
-  auto dw = torch::zeros({cd.Cout, (int64_t)K},
-                         xc.options().dtype(torch::kFloat32));
+  // zero-filled only on the paths that accumulate into it (atomic folds);
+  // the sliced path returns the sum over its partial slices instead
+  torch::Tensor dw;
+  auto zero_dw = [&]() {
+    dw = torch::zeros({cd.Cout, (int64_t)K},
+                      xc.options().dtype(torch::kFloat32));
+  };
   const bool fuse = bn_ab.defined() && bn_ab.numel() > 0;
   torch::Tensor ab;
   const float* abp = nullptr;
@@ -1074,11 +1079,14 @@ torch::Tensor conv2d_wgrad(torch::Tensor x, torch::Tensor go,
                         (int64_t)zstride * cd.Cout * K * 4 <=
                             (int64_t)512 * 1024 * 1024;
     torch::Tensor part;
-    float* outp = dw.data_ptr<float>();
+    float* outp;
     if (sliced) {
       part = torch::empty({(int64_t)zstride, (int64_t)cd.Cout, (int64_t)K},
                           xc.options().dtype(torch::kFloat32));
       outp = part.data_ptr<float>();
+    } else {
+      zero_dw();
+      outp = dw.data_ptr<float>();
     }
     auto L = [&](auto kern) {
       hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(),
@@ -1156,6 +1164,7 @@ torch::Tensor conv2d_wgrad(torch::Tensor x, torch::Tensor go,
     return dw.view({cd.Cout, cd.Cin, 3, 3});
   }
 
+  zero_dw();
   int planes = ((cd.Cout + 31) / 32) * ((K + 31) / 32);
   int64_t target_chunks = std::max<int64_t>(1, 2048 / std::max(planes, 1));
   int64_t chunk = std::max<int64_t>(128, (M + target_chunks - 1) /

@@ -22,6 +22,8 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 struct ConvDims {
   int N, Cin, D, H, W;
@@ -906,7 +908,241 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_s1_kernel(
   float* out = SLICED ? dw + (int64_t)blockIdx.z * cd.Cout * K : dw;
   const int ccol = lane & 15;          // ci col within fragment
   const int crow0 = (lane >> 4) * 4;   // co row
+#pragma unroll  // static acc index: the accumulators stay in registers
+  for (int tp = 0; tp < 27; ++tp) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int co = co0 + wi * 16 + crow0 + r;
+      const int ci = ci0 + wj * 16 + ccol;
+      if (co < cd.Cout && ci < cd.Cin) {
+        if (SLICED)
+          out[(int64_t)co * K + ci * 27 + tp] = acc[tp][r];
+        else
+          atomicAdd(&out[(int64_t)co * K + ci * 27 + tp], acc[tp][r]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Register-staged prefetch form of the stride-1 tap-reuse wgrad: staging is
+// split into "global -> registers" (pf_load) and "registers -> LDS with the
+// BN affine + ReLU" (pf_store). Chunk z+zstride's global loads are issued
+// before chunk z's MFMA loop and land in the SINGLE LDS buffer after the
+// loop's closing barrier, so LDS stays what conv3d_wgrad_s1_kernel uses.
+// Same thread<->row mapping, same tap order, same fold: bit-identical
+// output per launch geometry. Costs ~80 VGPRs at OWT=32 (2 waves/SIMD,
+// which is what the 512-block grid fills anyway). Routed for every
+// stride-1 tiling but <8, 128>; stride 2 (~230 VGPRs) has no room and
+// stays on conv3d_wgrad_s1_kernel.
+// ---------------------------------------------------------------------------
+template <int OWT, int CHUNK = 128, bool FUSE_BN = false, bool SLICED = false>
+__global__ __launch_bounds__(256) void conv3d_wgrad_s1_pf_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ go,
+    float* __restrict__ dw, ConvDims cd, int64_t nchunks, int64_t zstride,
+    const float* __restrict__ bn_ab = nullptr) {
+  constexpr int OHT = CHUNK / OWT;
+  constexpr int IW = OWT;
+  constexpr int W2 = IW + 4;
+  constexpr int H2 = OHT + 2;
+  constexpr int CT = 32, COT = 32;
+  constexpr int NXROWS = CT * 3 * H2;
+  constexpr int NGROWS = COT * OHT;
+  constexpr int NXI = (NXROWS + 255) / 256;   // x rows per thread
+  constexpr int NGI = (NGROWS + 255) / 256;   // go rows per thread
+  constexpr int NXV = IW / 8, NGV = OWT / 8;
+  __shared__ __bf16 sX[CT][3][H2][W2];
+  __shared__ __bf16 sGo[COT][CHUNK + LDA_PAD];
+
+  const int co0 = blockIdx.x * COT;
+  const int ci0 = blockIdx.y * CT;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wi = wave >> 1, wj = wave & 1;
+  const int row = lane & 15, kg = lane >> 4;
+
+  const int wtiles = (cd.OW + OWT - 1) / OWT;
+  const int htiles = (cd.OH + OHT - 1) / OHT;
+
+  f32x4 acc[27];
+#pragma unroll
+  for (int t = 0; t < 27; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
+
+  const int64_t HW = (int64_t)cd.H * cd.W;
+  const int64_t OHW = (int64_t)cd.OH * cd.OW;
+
+  // the BN affine of a thread's rows does not depend on the chunk
+  float a_c[NXI], b_c[NXI];
+#pragma unroll
+  for (int i = 0; i < NXI; ++i) {
+    a_c[i] = 1.f;
+    b_c[i] = 0.f;
+    const int ci = (tid + i * 256) / (3 * H2);
+    if (FUSE_BN && ci < CT && (ci0 + ci) < cd.Cin) {
+      a_c[i] = bn_ab[(ci0 + ci) * 2];
+      b_c[i] = bn_ab[(ci0 + ci) * 2 + 1];
+    }
+  }
+
+  // staged chunk: interior vectors + the 1 left / 3 right halo scalars
+  bf16x8 xv[NXI][NXV];
+  bf16x2 xl[NXI];   // [1] is column ow0-1
+  bf16x4 xr[NXI];   // [0..2] are columns ow0+IW .. ow0+IW+2
+  bf16x8 gv[NGI][NGV];
+
+  auto pf_load = [&](int64_t z) {
+    int64_t t = z;
+    const int wt = (int)(t % wtiles);
+    t /= wtiles;
+    const int ht = (int)(t % htiles);
+    t /= htiles;
+    const int od = (int)(t % cd.OD);
+    const int n = (int)(t / cd.OD);
+    const int oh0 = ht * OHT, ow0 = wt * OWT;
+    const __bf16* xn = x + (int64_t)n * cd.Cin * cd.D * HW;
+#pragma unroll
+    for (int i = 0; i < NXI; ++i) {
+      const int r = tid + i * 256;
+      const int hrow = r % H2;
+      const int a = (r / H2) % 3;
+      const int ci = r / (3 * H2);
+      const int id = od - 1 + a;
+      const int ih = oh0 - 1 + hrow;
+      const bool row_ok = r < NXROWS && (unsigned)id < (unsigned)cd.D &&
+                          (unsigned)ih < (unsigned)cd.H &&
+                          (ci0 + ci) < cd.Cin;
+      if (!row_ok) continue;
+      const __bf16* src = xn + ((int64_t)(ci0 + ci) * cd.D + id) * HW +
+                          (int64_t)ih * cd.W;
+      // halos as whole aligned words (rows are 16B multiples, ow0 a
+      // multiple of 8): a sub-word load would merge into a live register
+      // and make the later loads wait for it
+      if (ow0 > 0) xl[i] = *reinterpret_cast<const bf16x2*>(src + ow0 - 2);
+#pragma unroll
+      for (int v = 0; v < NXV; ++v)
+        xv[i][v] = *reinterpret_cast<const bf16x8*>(src + ow0 + v * 8);
+      if (ow0 + IW < cd.W)
+        xr[i] = *reinterpret_cast<const bf16x4*>(src + ow0 + IW);
+    }
+    const __bf16* gon = go + (int64_t)n * cd.Cout * cd.OD * OHW;
+#pragma unroll
+    for (int i = 0; i < NGI; ++i) {
+      const int r = tid + i * 256;
+      const int oh = oh0 + r % OHT;
+      const int co = r / OHT;
+      if (r >= NGROWS || (co0 + co) >= cd.Cout || oh >= cd.OH) continue;
+      const __bf16* src = gon + ((int64_t)(co0 + co) * cd.OD + od) * OHW +
+                          (int64_t)oh * cd.OW + ow0;
+#pragma unroll
+      for (int v = 0; v < NGV; ++v)
+        gv[i][v] = *reinterpret_cast<const bf16x8*>(src + v * 8);
+    }
+  };
+
+  auto pf_store = [&](int64_t z) {
+    int64_t t = z;
+    const int wt = (int)(t % wtiles);
+    t /= wtiles;
+    const int ht = (int)(t % htiles);
+    t /= htiles;
+    const int od = (int)(t % cd.OD);
+    const int oh0 = ht * OHT, ow0 = wt * OWT;
+#pragma unroll
+    for (int i = 0; i < NXI; ++i) {
+      const int r = tid + i * 256;
+      if (r >= NXROWS) continue;
+      const int hrow = r % H2;
+      const int a = (r / H2) % 3;
+      const int ci = r / (3 * H2);
+      const int id = od - 1 + a;
+      const int ih = oh0 - 1 + hrow;
+      __bf16* dst = &sX[ci][a][hrow][0];
+      const bool row_ok = (unsigned)id < (unsigned)cd.D &&
+                          (unsigned)ih < (unsigned)cd.H &&
+                          (ci0 + ci) < cd.Cin;
+      if (!row_ok) {
+#pragma unroll
+        for (int col = 0; col < W2; ++col) dst[col] = (__bf16)0.f;
+        continue;
+      }
+      auto tx = [&](__bf16 v) -> __bf16 {
+        if (!FUSE_BN) return v;
+        return (__bf16)fmaxf(a_c[i] * (float)v + b_c[i], 0.f);
+      };
+      dst[0] = (ow0 > 0) ? tx(xl[i][1]) : (__bf16)0.f;
+#pragma unroll
+      for (int v = 0; v < NXV; ++v)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dst[1 + v * 8 + j] = tx(xv[i][v][j]);
+      const bool right_ok = ow0 + IW < cd.W;
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+        dst[1 + IW + e] = right_ok ? tx(xr[i][e]) : (__bf16)0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < NGI; ++i) {
+      const int r = tid + i * 256;
+      if (r >= NGROWS) continue;
+      const int oh_off = r % OHT;
+      const int co = r / OHT;
+      __bf16* dst = &sGo[co][oh_off * OWT];
+      if ((co0 + co) >= cd.Cout || (oh0 + oh_off) >= cd.OH) {
+#pragma unroll
+        for (int j = 0; j < OWT; ++j) dst[j] = (__bf16)0.f;
+        continue;
+      }
+#pragma unroll
+      for (int v = 0; v < NGV; ++v)
+        *reinterpret_cast<bf16x8*>(dst + v * 8) = gv[i][v];
+    }
+  };
+
+  if ((int64_t)blockIdx.z < nchunks) pf_load(blockIdx.z);
+  for (int64_t z = blockIdx.z; z < nchunks; z += zstride) {
+    // vmcnt(0) on every path: pf_store waits inside its row branches
+    // only, and without this the compiler guards pf_load's registers
+    // with waits between the prefetch loads themselves
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    pf_store(z);
+    __syncthreads();
+    // next chunk's global loads fly under this chunk's MFMA loop
+    if (z + zstride < nchunks) pf_load(z + zstride);
+
 #pragma unroll 1
+    for (int ms = 0; ms < CHUNK / 32; ++ms) {
+      bf16x8 afrag;   // go[co16][m32]
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        afrag[j] = sGo[wi * 16 + row][ms * 32 + kg * 8 + j];
+      const int mbase = ms * 32 + kg * 8;
+      const int oh_off = mbase / OWT;
+      const int ow_off = mbase % OWT;
+#pragma unroll
+      for (int kd = 0; kd < 3; ++kd) {
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) {
+            bf16x8 bfrag;
+            const __bf16* src = &sX[wj * 16 + row][kd][oh_off + kh]
+                                   [ow_off + kw];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bfrag[j] = src[j];
+            acc[(kd * 3 + kh) * 3 + kw] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    afrag, bfrag, acc[(kd * 3 + kh) * 3 + kw], 0, 0, 0);
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  const int K = cd.Cin * 27;
+  float* out = SLICED ? dw + (int64_t)blockIdx.z * cd.Cout * K : dw;
+  const int ccol = lane & 15;
+  const int crow0 = (lane >> 4) * 4;
+#pragma unroll
   for (int tp = 0; tp < 27; ++tp) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1068,7 +1304,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_s1_db_kernel(
   const int K = cd.Cin * 27;
   const int ccol = lane & 15;
   const int crow0 = (lane >> 4) * 4;
-#pragma unroll 1
+#pragma unroll  // static acc index: the accumulators stay in registers
   for (int tp = 0; tp < 27; ++tp) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1209,8 +1445,13 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
   cd.OD = (int)g.size(2); cd.OH = (int)g.size(3); cd.OW = (int)g.size(4);
   int K = cd.Cin * 27;
   int64_t M = (int64_t)cd.N * cd.OD * cd.OH * cd.OW;
-  auto dw = torch::zeros({cd.Cout, (int64_t)K},
-                         xc.options().dtype(torch::kFloat32));
+  // zero-filled only on the paths that accumulate into it (atomic folds);
+  // the sliced path returns the sum over its partial slices instead
+  torch::Tensor dw;
+  auto zero_dw = [&]() {
+    dw = torch::zeros({cd.Cout, (int64_t)K},
+                      xc.options().dtype(torch::kFloat32));
+  };
   const bool fuse = bn_ab.defined() && bn_ab.numel() > 0;
   torch::Tensor ab;
   const float* abp = nullptr;
@@ -1228,6 +1469,7 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
     const int GOL = CI1_OHT * cd.OW + 8;
     size_t lds = (size_t)(3 * H2 * W2 + 32 * GOL) * sizeof(__bf16);
     if (lds <= 64 * 1024) {
+      zero_dw();
       dim3 grid(cd.N, od_groups, (cd.Cout + 31) / 32);
       hipLaunchKernelGGL(conv3d_wgrad_ci1_kernel, grid, dim3(256), lds,
                          current_stream(),
@@ -1254,7 +1496,10 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
     int64_t nchunks = (int64_t)cd.N * cd.OD * htiles * wtiles;
     // blocks-in-flight target: swept on MI355X (r2) — 512 won (41.0
     // ms/step vs 42.1 at the old 768; >=1024 loses to atomic-fold
-    // contention, <=256 underfills the chip). COINN_WGRAD_Z overrides.
+    // contention, <=256 underfills the chip). Re-swept with the
+    // accumulators in registers and the sliced fold: 512 still wins
+    // (29.4 ms/step vs 30.9 at 768; profiles/wgrad_registers_ab.md).
+    // COINN_WGRAD_Z overrides.
     static const int zbase = []() {
       const char* e = getenv("COINN_WGRAD_Z");
       return e ? atoi(e) : 512;
@@ -1267,11 +1512,14 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
                         (int64_t)zstride * cd.Cout * K * 4 <=
                             (int64_t)512 * 1024 * 1024;
     torch::Tensor part;
-    float* outp = dw.data_ptr<float>();
+    float* outp;
     if (sliced) {
       part = torch::empty({(int64_t)zstride, (int64_t)cd.Cout, (int64_t)K},
                           xc.options().dtype(torch::kFloat32));
       outp = part.data_ptr<float>();
+    } else {
+      zero_dw();
+      outp = dw.data_ptr<float>();
     }
     dim3 grid(co_t, ci_t, (unsigned)zstride);
     if (stride == 1 && variant == 1) {
@@ -1287,21 +1535,32 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
       });
       return dw.view({cd.Cout, cd.Cin, 3, 3, 3});
     }
-    // the whole instance family: tiling x stride x fused-BN x sliced
+    // the whole instance family: tiling x stride x fused-BN x sliced.
+    // Stride 1 runs the register-staged prefetch form, except the 8-wide
+    // chunk-128 tiling: it stages 7 slab rows per thread, and holding a
+    // prefetched copy of them would drop it to 1 wave/SIMD.
     dispatch_wgrad_tile(OWT, chunk, [&](auto owt, auto ch) {
+      constexpr int owt_v = decltype(owt)::value;
+      constexpr int ch_v = decltype(ch)::value;
       dispatch_bool(stride == 2, [&](auto s2) {
+        constexpr bool s2_v = decltype(s2)::value;
         dispatch_bool(fuse, [&](auto fz) {
           dispatch_bool(sliced, [&](auto sl) {
-            hipLaunchKernelGGL(
-                (conv3d_wgrad_s1_kernel<decltype(owt)::value,
-                                        decltype(s2)::value ? 2 : 1,
-                                        decltype(ch)::value,
-                                        decltype(fz)::value,
-                                        decltype(sl)::value>),
-                grid, dim3(256), 0, current_stream(),
-                reinterpret_cast<const __bf16*>(xc.data_ptr()),
-                reinterpret_cast<const __bf16*>(g.data_ptr()), outp, cd,
-                nchunks, zstride, abp);
+            auto launch = [&](auto kern) {
+              hipLaunchKernelGGL(
+                  kern, grid, dim3(256), 0, current_stream(),
+                  reinterpret_cast<const __bf16*>(xc.data_ptr()),
+                  reinterpret_cast<const __bf16*>(g.data_ptr()), outp, cd,
+                  nchunks, zstride, abp);
+            };
+            if constexpr (!s2_v && !(owt_v == 8 && ch_v == 128))
+              launch(conv3d_wgrad_s1_pf_kernel<owt_v, ch_v,
+                                               decltype(fz)::value,
+                                               decltype(sl)::value>);
+            else
+              launch(conv3d_wgrad_s1_kernel<owt_v, s2_v ? 2 : 1, ch_v,
+                                            decltype(fz)::value,
+                                            decltype(sl)::value>);
           });
         });
       });
@@ -1311,6 +1570,7 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
   }
 
   // fallback: split-K implicit GEMM (any shape / stride)
+  zero_dw();
   int planes = ((cd.Cout + 31) / 32) * ((K + 31) / 32);
   int64_t target_chunks = std::max<int64_t>(1, 2048 / std::max(planes, 1));
   int64_t chunk = std::max<int64_t>(128, (M + target_chunks - 1) /
