@@ -1,15 +1,19 @@
 // Conv3d fwd/dgrad with spatial-slab tap reuse (stride 1 and stride-2 fwd).
 // The igemm formulation re-gathers x once per (ci,tap) — 27x traffic.
-// Here a block stages one input spatial slab [CTILE][3][H2][W2] per
-// channel tile and computes the whole K loop from it:
-//   - slab rows are staged with 16-byte vector loads (interior columns are
-//     in-bounds by construction since OWT divides the output width);
-//   - the A fragments read the slab at base(m) + sKtab[k], a precomputed
-//     u16 offset table (tap decode off the hot path);
+// Here a block stages one input spatial slab per channel tile and computes
+// the whole K loop from it:
+//   - CTILE >= 16: the slab is channel-innermost, [3][H2][W2][CTILE], and K
+//     inside a tile runs (tap, local channel), so an A fragment is one
+//     16-byte LDS read at a wave-uniform tap offset. Rows are fetched as
+//     16-byte vectors along w, BN+ReLU applied per channel, and 4 or 8
+//     adjacent channels interleaved into one wide LDS store;
+//   - CTILE 1 (first layer): the slab is [3][H2][W2] and the A fragments
+//     read it at base(m) + sKtab[k], a precomputed u16 tap-offset table;
 //   - the B fragments are contiguous 16-byte global loads from the small
 //     L2-resident prepared-weight matrix WB[ncol][kts*KT_PAD] (fwd: w
-//     reshaped; dgrad: tap-flipped + transposed; each CTILE-channel block
-//     zero-padded to a 32-multiple so MFMA k-windows never straddle tiles).
+//     reordered; dgrad: tap-flipped + transposed; each CTILE-channel block
+//     zero-padded to a 32-multiple so MFMA k-windows never straddle tiles),
+//     loaded one k-step ahead of the MFMAs that use them.
 // Geometry: out tile = (OWT*OHT) m x 32 ncol; 4 waves x MPW m-fragments x
 // 2 ncol-fragments; chunk = (n, d, h-tile, w-tile) of the OUTPUT grid.
 // STRIDE=2 stages the strided window (IW = 2*OWT interior) with CTILE=16.
@@ -18,6 +22,7 @@
 #include <hip/hip_bf16.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
@@ -33,6 +38,15 @@ struct SpDims {
 #define LDA_PAD 8
 #endif
 
+// Waves per SIMD the register allocation must leave room for. The
+// small-slab chunk-64 instances are not LDS-limited, and the unrolled tap
+// loop would otherwise trade their occupancy for hoisted loads.
+constexpr int sp_min_waves(int ctile, int chunk, int ncolt, bool fuse_bn) {
+  if (ctile < 16 || chunk != 64) return 1;
+  if (ncolt == 128 || fuse_bn) return 4;
+  return ncolt == 32 ? 6 : 5;
+}
+
 // FUSE_BN: normalize-on-load — the staged input is the PREVIOUS block's
 // raw conv output; z = relu(a[c]*x + b[c]) is applied per element during
 // staging (a = gamma*rstd, b = beta - mean*a, exactly bn_normalize's
@@ -45,7 +59,9 @@ struct SpDims {
 template <int OWT, int STRIDE, int CTILE,
           int CHUNK = (STRIDE == 1 ? 256 : 128), bool FUSE_BN = false,
           int SMODE = 0, int NCOLT = 32>
-__global__ __launch_bounds__(256) void conv3d_spatial_kernel(
+__global__ __launch_bounds__(
+    256, sp_min_waves(CTILE, CHUNK, NCOLT, FUSE_BN))
+void conv3d_spatial_kernel(
     const __bf16* __restrict__ in, const __bf16* __restrict__ wb,
     __bf16* __restrict__ out, SpDims sd, int64_t nchunks,
     const float* __restrict__ bn_ab = nullptr,
@@ -58,8 +74,14 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
   static_assert(MPW >= 1, "chunk too small");
   constexpr int KT_PAD = ((CTILE * 27 + 31) / 32) * 32;
   constexpr int NCF = NCOLT / 16;  // ncol fragments per wave
-  __shared__ __bf16 sX[CTILE][3][H2][W2];
-  __shared__ unsigned short sKtab[KT_PAD + 8];
+  constexpr bool CL = CTILE >= 16;  // channel-innermost slab, b128 A reads
+  static_assert(!CL || (CTILE == 32 && STRIDE == 1) || CTILE == 16,
+                "channel-innermost tiles: 32 (stride 1) or 16");
+  static_assert(!CL || (CHUNK / 4) % OWT == 0 || OWT == 8,
+                "a wave's fragments must start on a tile row");
+  __shared__ __attribute__((aligned(16))) __bf16 sXf[CTILE * 3 * H2 * W2];
+  __shared__ unsigned short sKtab[CL ? 8 : KT_PAD + 8];
+  auto sX = reinterpret_cast<__bf16(*)[3][H2][W2]>(sXf);  // !CL view
 
   const int ncol0 = blockIdx.y * NCOLT;
   const int tid = threadIdx.x;
@@ -79,7 +101,7 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
   const int oh0 = ht * OHT, ow0 = wt * OWT;
 
   // k -> slab element offset (pad entries -> 0: their weights are zero)
-  for (int k = tid; k < KT_PAD; k += 256) {
+  for (int k = tid; !CL && k < KT_PAD; k += 256) {
     unsigned short off = 0;
     if (k < CTILE * 27) {
       const int cl = k / 27;
@@ -100,6 +122,191 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
   const int64_t in_n = (int64_t)n * sd.KCH * sd.D * HW;
   const int kts = (sd.KCH + CTILE - 1) / CTILE;
 
+  if constexpr (CL) {
+    // ---- channel-innermost slab [3][H2][W2][CTILE] --------------------
+    // K inside a channel tile runs (tap, local channel), so the 8 k of
+    // lane (row, kg) are ONE 16-byte word of the slab. A ds_read_b128 is
+    // served in four groups of 16 lanes, each holding 16 distinct rows
+    // under two kg values; the XOR swizzles below spread every group over
+    // all 64 banks:
+    //   CTILE 32 (64 B per position):            chunk    ^= 2 * bit2(w)
+    //   CTILE 16, stride 2 (rows 64 B apart):    position ^= bit3(w)
+    //   CTILE 16, stride 1 (rows 32 B apart):    conflict-free as it is
+    auto slab_off = [](int a, int h, int w, int cl) -> int {
+      int pos = w, chunk = cl >> 3;
+      if (CTILE == 32) chunk ^= ((w >> 2) & 1) << 1;
+      if (CTILE == 16 && STRIDE == 2) pos ^= (w >> 3) & 1;
+      return ((a * H2 + h) * W2 + pos) * CTILE + chunk * 8 + (cl & 7);
+    };
+    // A address = lanew[c] + (fragment, tap-plane) constants: the swizzle
+    // bits of w depend on (row, c) only, fragments start 16 or 32 columns
+    // apart and tap planes whole rows apart
+    const int m_l = wave * (MPW * 16) + row;
+    int lanew[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      lanew[c] = slab_off(0, STRIDE * (m_l / OWT), STRIDE * (m_l % OWT) + c,
+                          (CTILE == 32 ? kg : (kg & 1)) * 8);
+    auto frag_off = [](int i) -> int {
+      return (STRIDE * ((i * 16) / OWT) * W2 + STRIDE * ((i * 16) % OWT)) *
+             CTILE;
+    };
+
+    // B: lane (col = row, kg) reads 8 consecutive k of its column; channel
+    // tiles are contiguous in WB, so k-step g = kt*KS + ks sits at g*32.
+    // WB has zero rows up to the next multiple of 128 columns, so a ragged
+    // column tile needs no bounds check here.
+    constexpr int KS = KT_PAD / 32;
+    const __bf16* wbl = wb + (int64_t)(ncol0 + row) * sd.Kpad + kg * 8;
+    auto bload = [&](int j, int g) -> bf16x8 {
+      return *reinterpret_cast<const bf16x8*>(
+          wbl + (int64_t)j * 16 * sd.Kpad + (int64_t)g * 32);
+    };
+    constexpr bool BPF = NCF <= 2;  // one-deep B register pipeline
+    bf16x8 bcur[NCF];
+#pragma unroll
+    for (int j = 0; BPF && j < NCF; ++j)
+      bcur[j] = bload(j, 0);
+
+    constexpr int NV = IW / 8;  // 8-column vectors per interior row
+    // a thread carries one 8-column vector of CG adjacent channels and
+    // stores 8 interleaved CG-channel words (lanes run over channel group,
+    // then column vector: 2- to 4-way conflicted stores, but the row-
+    // interleaved conflict-free order lost, profiles/spatial_b128_ab.md)
+    constexpr int CG = (3 * H2 * NV * (CTILE / 8) >= 256) ? 8 : 4;
+    constexpr int NCG = CTILE / CG;
+    constexpr int NITEM = 3 * H2 * NV * NCG;
+    constexpr int NHALO = STRIDE == 1 ? 2 : 1;  // halo columns the taps read
+    const int iw0 = STRIDE * ow0;
+    const bool wvec = (sd.W & 7) == 0;  // rows 16-byte aligned
+
+    for (int kt = 0; kt < kts; ++kt) {
+      if (kt) __syncthreads();
+      for (int it = tid; it < NITEM; it += 256) {
+        const int cg = it % NCG;
+        const int v = (it / NCG) % NV;
+        const int hrow = (it / (NCG * NV)) % H2;
+        const int a = it / (NCG * NV * H2);
+        const int id = STRIDE * td - 1 + a;
+        const int ih = STRIDE * oh0 - 1 + hrow;
+        const int iw = iw0 + v * 8;
+        const bool row_ok = (unsigned)id < (unsigned)sd.D &&
+                            (unsigned)ih < (unsigned)sd.H;
+        __bf16 t[CG][8];
+#pragma unroll
+        for (int cc = 0; cc < CG; ++cc) {
+          const int ch = kt * CTILE + cg * CG + cc;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) t[cc][j] = (__bf16)0.f;
+          if (row_ok && ch < sd.KCH) {
+            const __bf16* src = in + in_n + ((int64_t)ch * sd.D + id) * HW +
+                                (int64_t)ih * sd.W;
+            float a_c = 1.f, b_c = 0.f;
+            if (FUSE_BN) { a_c = bn_ab[ch * 2]; b_c = bn_ab[ch * 2 + 1]; }
+            auto tx = [&](__bf16 x) -> __bf16 {
+              if (!FUSE_BN) return x;
+              return (__bf16)fmaxf(a_c * (float)x + b_c, 0.f);
+            };
+            if (wvec && iw + 8 <= sd.W) {
+              const bf16x8 vec = *reinterpret_cast<const bf16x8*>(src + iw);
+#pragma unroll
+              for (int j = 0; j < 8; ++j) t[cc][j] = tx(vec[j]);
+            } else {
+#pragma unroll
+              for (int j = 0; j < 8; ++j)
+                if (iw + j < sd.W) t[cc][j] = tx(src[iw + j]);
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          __bf16* dst = sXf + slab_off(a, hrow, 1 + v * 8 + j, cg * CG);
+          if constexpr (CG == 8) {
+            bf16x8 o;
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) o[cc] = t[cc][j];
+            *reinterpret_cast<bf16x8*>(dst) = o;
+          } else {
+            bf16x4 o;
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) o[cc] = t[cc][j];
+            *reinterpret_cast<bf16x4*>(dst) = o;
+          }
+        }
+      }
+      // halo columns: one element per (plane, row, side, channel)
+      for (int it = tid; it < 3 * H2 * NHALO * CTILE; it += 256) {
+        const int cl = it % CTILE;
+        const int side = (it / CTILE) % NHALO;
+        const int hrow = (it / (CTILE * NHALO)) % H2;
+        const int a = it / (CTILE * NHALO * H2);
+        const int col = side ? IW + 1 : 0;
+        const int id = STRIDE * td - 1 + a;
+        const int ih = STRIDE * oh0 - 1 + hrow;
+        const int iw = iw0 - 1 + col;
+        const int ch = kt * CTILE + cl;
+        __bf16 val = (__bf16)0.f;
+        if ((unsigned)id < (unsigned)sd.D && (unsigned)ih < (unsigned)sd.H &&
+            (unsigned)iw < (unsigned)sd.W && ch < sd.KCH) {
+          val = in[in_n + ((int64_t)ch * sd.D + id) * HW +
+                   (int64_t)ih * sd.W + iw];
+          if (FUSE_BN)
+            val = (__bf16)fmaxf(
+                bn_ab[ch * 2] * (float)val + bn_ab[ch * 2 + 1], 0.f);
+        }
+        sXf[slab_off(a, hrow, col, cl)] = val;
+      }
+      __syncthreads();
+
+      // ---- k-steps of 32: one tap x 32 channels, or two taps x 16 -----
+      // the next step's B fragments are in flight under this step's MFMAs
+      // (narrow instances; the wide ones have no registers to spare for it)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        if constexpr (!BPF) {
+#pragma unroll
+          for (int j = 0; j < NCF; ++j)
+            bcur[j] = bload(j, kt * KS + ks);
+        }
+        const bool more = BPF && (ks + 1 < KS || kt + 1 < kts);
+        bf16x8 bnext[NCF];
+        if (more) {
+#pragma unroll
+          for (int j = 0; j < NCF; ++j)
+            bnext[j] = bload(j, kt * KS + ks + 1);
+        }
+        int lk;
+        if (CTILE == 32) {
+          lk = lanew[ks % 3] + ((ks / 9) * H2 + (ks / 3) % 3) * W2 * CTILE;
+        } else {
+          // taps 2ks (kg 0,1) and 2ks+1 (kg 2,3); the 28th tap has zero
+          // weights and re-reads the 27th
+          const int t0 = 2 * ks, t1 = 2 * ks + 1 < 27 ? 2 * ks + 1 : 26;
+          const int l0 =
+              lanew[t0 % 3] + ((t0 / 9) * H2 + (t0 / 3) % 3) * W2 * CTILE;
+          const int l1 =
+              lanew[t1 % 3] + ((t1 / 9) * H2 + (t1 / 3) % 3) * W2 * CTILE;
+          lk = (kg >> 1) ? l1 : l0;
+        }
+        bf16x8 afrag[MPW];
+#pragma unroll
+        for (int i = 0; i < MPW; ++i)
+          afrag[i] =
+              *reinterpret_cast<const bf16x8*>(sXf + lk + frag_off(i));
+#pragma unroll
+        for (int i = 0; i < MPW; ++i)
+#pragma unroll
+          for (int j = 0; j < NCF; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag[i], bcur[j], acc[i][j], 0, 0, 0);
+        if (more) {
+#pragma unroll
+          for (int j = 0; j < NCF; ++j) bcur[j] = bnext[j];
+        }
+      }
+    }
+  } else {
+  // CTILE 1 (first layer): w-innermost slab, A gathered through sKtab
   for (int kt = 0; kt < kts; ++kt) {
     // ---- stage the slab row-wise (16B interior, scalar halo) ----------
     constexpr int NROWS = CTILE * 3 * H2;
@@ -179,8 +386,12 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
               afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
     }
   }
+  }
 
   // ---- epilogue: out[n][col][td][oh0+][ow0+] --------------------------
+  // a lane's 4 consecutive m share an output row (OWT is a multiple of 8):
+  // one 8-byte store when the rows are 8-byte aligned (TW % 4 == 0)
+  const bool pack4 = (sd.TW & 3) == 0;
   const int64_t THW = (int64_t)sd.TH * sd.TW;
   const int64_t out_n = (int64_t)n * sd.NCOL * sd.TD * THW;
   const int ccol = lane & 15;
@@ -193,6 +404,27 @@ __global__ __launch_bounds__(256) void conv3d_spatial_kernel(
     for (int j = 0; j < NCF; ++j) {
       const int col = ncol0 + j * 16 + ccol;
       if (col >= sd.NCOL) continue;
+      if (pack4) {
+        const int m = (wave * MPW + i) * 16 + crow0;
+        const int oh = oh0 + m / OWT;
+        const int ow = ow0 + m % OWT;
+        if (oh < sd.TH && ow < sd.TW) {  // ow % 4 == 0: ow + 3 < TW too
+          bf16x4 o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            o[r] = (__bf16)acc[i][j][r];
+            if (SMODE == 1) {
+              const float vb = (float)o[r];
+              cs[j] += vb;
+              css[j] += vb * vb;
+            }
+          }
+          *reinterpret_cast<bf16x4*>(
+              out + out_n + ((int64_t)col * sd.TD + td) * THW +
+              (int64_t)oh * sd.TW + ow) = o;
+        }
+        continue;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = (wave * MPW + i) * 16 + crow0 + r;
@@ -318,21 +550,42 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
   return p;
 }
 
-// WB layout: [NCOL][kts * KT_PAD]; channel-tile block kt holds the CTILE*27
-// weights for channels [kt*CTILE, (kt+1)*CTILE), zero-padded to KT_PAD.
-static torch::Tensor prep_wb(torch::Tensor w_flat2d, int KCH,
-                             const SpatialPlan& p) {
-  const int ctile = p.ctile;
-  int ncol = (int)w_flat2d.size(0);
-  int kt_pad = (ctile * 27 + 31) / 32 * 32;
-  int kts = (KCH + ctile - 1) / ctile;
-  auto wb = torch::zeros({ncol, (int64_t)kts * kt_pad}, w_flat2d.options());
-  for (int kt = 0; kt < kts; ++kt) {
-    int64_t k0 = (int64_t)kt * ctile * 27;
-    int64_t klen = (int64_t)std::min(KCH - kt * ctile, ctile) * 27;
-    wb.narrow(1, (int64_t)kt * kt_pad, klen).copy_(
-        w_flat2d.narrow(1, k0, klen));
-  }
+// WB layout: [NCOL][kts][KT_PAD], k inside a channel tile = tap*CTILE + local
+// channel (CTILE 1: just the tap); taps >= 27 and channels >= KCH are zero.
+// Rows [NCOL, next multiple of 128) exist and are zero, so the widest column
+// tile of the last grid row reads in bounds without a check.
+// One launch writes every element straight from the bf16 weight
+// w[Cout][Cin][27]: forward reads w[col][ch][tap], dgrad (KCH = Cout,
+// NCOL = Cin) the tap-flipped transpose w[ch][col][26 - tap].
+__global__ __launch_bounds__(256) void conv3d_spatial_prep_wb_kernel(
+    const __bf16* __restrict__ w, __bf16* __restrict__ wb, int ncol, int kch,
+    int ctile, int kt_pad, int kpad, int dgrad) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (ncol + 127) / 128 * 128 * kpad) return;
+  const int col = idx / kpad, k = idx - col * kpad;
+  const int kt = k / kt_pad, kk = k - kt * kt_pad;
+  const int tap = kk / ctile, ch = kt * ctile + kk % ctile;
+  __bf16 v = (__bf16)0.f;
+  if (tap < 27 && ch < kch && col < ncol)
+    v = dgrad ? w[((int64_t)ch * ncol + col) * 27 + 26 - tap]
+              : w[((int64_t)col * kch + ch) * 27 + tap];
+  wb[idx] = v;
+}
+
+static torch::Tensor prep_wb(torch::Tensor w, int ncol, int KCH,
+                             const SpatialPlan& p, bool dgrad) {
+  const int kt_pad = (p.ctile * 27 + 31) / 32 * 32;
+  const int kts = (KCH + p.ctile - 1) / p.ctile;
+  const int kpad = kts * kt_pad;
+  const int rows = (ncol + 127) / 128 * 128;
+  TORCH_CHECK((int64_t)rows * kpad < (int64_t)1 << 31, "WB too large");
+  auto wb = torch::empty({rows, (int64_t)kpad}, w.options());
+  hipLaunchKernelGGL(conv3d_spatial_prep_wb_kernel,
+                     dim3((rows * kpad + 255) / 256), dim3(256), 0,
+                     current_stream(),
+                     reinterpret_cast<const __bf16*>(w.data_ptr()),
+                     reinterpret_cast<__bf16*>(wb.data_ptr()), ncol, KCH,
+                     p.ctile, kt_pad, kpad, dgrad ? 1 : 0);
   return wb;
 }
 
@@ -444,8 +697,8 @@ static std::vector<torch::Tensor> spatial_fwd(torch::Tensor x,
   auto odim = [&](int i) { return ((int)xc.size(i) + 2 - 3) / stride + 1; };
   SpDims sd = make_spdims(xc, (int)wc.size(0), odim(2), odim(3), odim(4));
   const SpatialPlan plan = plan_spatial(sd, stride, mode);
-  auto wb = prep_wb(wc.reshape({sd.NCOL, (int64_t)sd.KCH * 27}), sd.KCH,
-                    plan);
+  TORCH_CHECK(wc.size(1) == sd.KCH, "weight/input channel mismatch");
+  auto wb = prep_wb(wc, sd.NCOL, sd.KCH, plan, false);
   sd.Kpad = (int)wb.size(1);
   auto out = torch::empty({sd.N, sd.NCOL, sd.TD, sd.TH, sd.TW},
                           xc.options());
@@ -491,11 +744,10 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
   auto wc = w.to(torch::kBFloat16).contiguous();
   SpDims sd = make_spdims(g, (int)in_shape[1], (int)in_shape[2],
                           (int)in_shape[3], (int)in_shape[4]);
-  int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
-  auto wf = wc.reshape({Cout, Cin, 27}).flip(-1).permute({1, 0, 2})
-                .reshape({Cin, (int64_t)Cout * 27}).contiguous();
+  TORCH_CHECK(wc.size(0) == sd.KCH && wc.size(1) == sd.NCOL,
+              "weight/grad channel mismatch");
   const SpatialPlan plan = plan_spatial(sd, 1, SP_DGRAD);
-  auto wb = prep_wb(wf, Cout, plan);
+  auto wb = prep_wb(wc, sd.NCOL, sd.KCH, plan, true);
   sd.Kpad = (int)wb.size(1);
   auto dx = torch::empty(in_shape, g.options());
   launch_spatial(g, wb, dx, sd, 1, SP_DGRAD, plan);

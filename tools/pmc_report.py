@@ -23,3 +23,12 @@ for name, c in agg.items():
               'SQ_ACTIVE_INST_VALU']:
         v = c.get(k, 0)
         print(f"   {k:22s} {v/wc*100:5.1f}% of wave cycles")
+    # LDS array: all active cycles, and the share that is bank-conflict
+    # replay (collect these in a run of their own)
+    if 'SQ_LDS_IDX_ACTIVE' in c:
+        act, conf = c['SQ_LDS_IDX_ACTIVE'], c.get('SQ_LDS_BANK_CONFLICT', 0)
+        print(f"   {'SQ_LDS_IDX_ACTIVE':22s} {act:.4g} cycles"
+              + (f" ({act / c['SQ_BUSY_CYCLES'] * 100:5.1f}% of SQ busy)"
+                 if c.get('SQ_BUSY_CYCLES') else ''))
+        print(f"   {'SQ_LDS_BANK_CONFLICT':22s} {conf:.4g} cycles "
+              f"({conf / max(act, 1) * 100:5.1f}% of LDS active)")
