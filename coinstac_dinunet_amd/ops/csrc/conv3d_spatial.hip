@@ -14,9 +14,12 @@
 //     reordered; dgrad: tap-flipped + transposed; each CTILE-channel block
 //     zero-padded to a 32-multiple so MFMA k-windows never straddle tiles),
 //     loaded one k-step ahead of the MFMAs that use them.
-// Geometry: out tile = (OWT*OHT) m x 32 ncol; 4 waves x MPW m-fragments x
-// 2 ncol-fragments; chunk = (n, d, h-tile, w-tile) of the OUTPUT grid.
+// Geometry: out tile = (OWT*OHT) m x NCOLT ncol (32, 64 or 128); 4 waves x
+// MPW m-fragments x NCOLT/16 ncol-fragments; chunk = (n, d, h-tile, w-tile)
+// of the OUTPUT grid.
 // STRIDE=2 stages the strided window (IW = 2*OWT interior) with CTILE=16.
+// The stride-2 dgrad (conv3d_dgrad_s2_sp_kernel, below) is its own kernel:
+// 8 parity classes of a dx brick from one staged go slab.
 #include "common.h"
 
 #include <hip/hip_bf16.h>
@@ -530,6 +533,10 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
   // stride-1 layers — 36.7 vs 37.5 ms/step on the flagship (r2)
   if (stride == 1 && sd.NCOL >= 64 && (mode == SP_PLAIN || fused))
     p.gcolt = 64;
+  // stride-2 chunk-128 forwards: the 57 KB slab feeds only 56 MFMAs per
+  // wave at 32 columns, so every epilogue has 64- and 128-column instances
+  // (grid and kernel column tile are the same number here)
+  if (stride == 2 && sd.NCOL >= 64) p.gcolt = sd.NCOL >= 128 ? 128 : 64;
   // small images (d8-class): 64-position chunks keep the grid dense;
   // wide-column instances halve the slab-staging redundancy there
   // (PMC: 86% SQ_WAIT on the 32-col chunk-64 forms)
@@ -624,6 +631,11 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
     else if (mode == SP_FUSED) f(std::true_type{}, IntC<0>{});
     else f(std::false_type{}, IntC<0>{});
   };
+  auto with_ncolt = [&](auto f) {
+    if (p.ncolt == 128) f(IntC<128>{});
+    else if (p.ncolt == 64) f(IntC<64>{});
+    else f(IntC<32>{});
+  };
   const std::false_type plain{};
   if (p.ctile == 1) {
     // single-channel (first-layer) instances: one 32-k-step covers the
@@ -645,11 +657,6 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
   } else if (p.chunk == 64) {
     // every epilogue x {32, 64, 128} columns x stride
     with_epilogue([&](auto fz, auto sm) {
-      auto with_ncolt = [&](auto f) {
-        if (p.ncolt == 128) f(IntC<128>{});
-        else if (p.ncolt == 64) f(IntC<64>{});
-        else f(IntC<32>{});
-      };
       with_ncolt([&](auto nc) {
         if (stride == 1)
           K(IntC<8>{}, IntC<1>{}, IntC<32>{}, IntC<64>{}, fz, sm, nc);
@@ -658,9 +665,12 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
       });
     });
   } else if (stride == 2) {
+    // chunk 128: every epilogue x {32, 64, 128} columns x OWT
     with_epilogue([&](auto fz, auto sm) {
-      with_owt([&](auto owt) {
-        K(owt, IntC<2>{}, IntC<16>{}, IntC<128>{}, fz, sm, IntC<32>{});
+      with_ncolt([&](auto nc) {
+        with_owt([&](auto owt) {
+          K(owt, IntC<2>{}, IntC<16>{}, IntC<128>{}, fz, sm, nc);
+        });
       });
     });
   } else if (p.ncolt == 64) {
@@ -755,183 +765,289 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
 }
 
 // ---------------------------------------------------------------------------
-// Stride-2 DGRAD, parity classes through the spatial-slab structure.
-// dx decomposes by (id,ih,iw) mod 2 into 8 dense sub-problems; within a
-// class the taps shift the go window by only {0,+1} per axis, so a block
-// stages a TINY go slab [co32][2][OHT+1][OWT+1] once per 32-co tile and
-// computes K = 32*T tap-products from it (T = 1..8 taps per class). The
-// per-class weight matrix WBc[ci][co*T + r] is prepared host-side
-// (tap-gathered), contiguous 16B per lane. blockIdx.z = class.
+// Stride-2 DGRAD: all 8 parity classes of a tile from ONE staged go slab.
+// dx decomposes by (id,ih,iw) mod 2 into 8 dense sub-problems ("classes");
+// per axis, dx index i = 2i' + p takes
+//   p = 0: tap k = 1 at go index i'
+//   p = 1: tap k = 0 at go index i' + 1, and tap k = 2 at go index i'
+// so the 27 taps read the go window at only 8 shifts (dod,doh,dow) in
+// {0,1}^3. A block owns OHT x OWT sub-grid positions at sub-grid depth id'
+// (a 2 x 2*OHT x 2*OWT brick of dx) and stages the channel-innermost slab
+// [2][OHT+1][OWT+1 (row pitch OWT+4)][32 co] once per 32-co tile. K runs
+// (tap, local co): a k-step of 32 is one tap, and lane (row, kg) reads its
+// 8 k as one 16-byte LDS word at lanew[dow] + (shift, fragment) constants.
+// Each shifted fragment is read once and multiplied into every class that
+// has a tap at that shift: per wave 8 x 4 A reads and 27 B loads feed
+// 27 x 4 = 108 MFMAs on 8 x 4 accumulator fragments (128 registers).
+// A lane holds the c = 0 and c = 1 accumulators of the same 4 iw', which
+// are 8 consecutive dx elements of one row: one 16-byte store.
 // ---------------------------------------------------------------------------
+// class = parity bits (a, b, c) of (id, ih, iw), shift = (dod, doh, dow),
+// both packed depth-major into 3 bits
+__host__ __device__ constexpr bool s2_feeds(int cls, int s) {
+  return (s & ~cls) == 0;  // only odd-parity axes have a shifted tap
+}
+
+__host__ __device__ constexpr int s2_tap(int cls, int s) {
+  int tap = 0;
+  for (int ax = 2; ax >= 0; --ax) {
+    const int par = (cls >> ax) & 1, sh = (s >> ax) & 1;
+    tap = tap * 3 + (par ? (sh ? 0 : 2) : 1);
+  }
+  return tap;
+}
+
+// WB slot of (class, shift): class-major, shifts ascending inside a class
+__host__ __device__ constexpr int s2_slot(int cls, int s) {
+  int n = 0;
+  for (int c2 = 0; c2 < cls; ++c2)
+    n += 1 << (((c2 >> 2) & 1) + ((c2 >> 1) & 1) + (c2 & 1));
+  for (int s2 = 0; s2 < s; ++s2) n += s2_feeds(cls, s2) ? 1 : 0;
+  return n;
+}
+
+struct S2TapTable { int tap[27]; };
+constexpr S2TapTable s2_tap_table() {
+  S2TapTable t{};
+  for (int cls = 0; cls < 8; ++cls)
+    for (int s = 0; s < 8; ++s)
+      if (s2_feeds(cls, s)) t.tap[s2_slot(cls, s)] = s2_tap(cls, s);
+  return t;
+}
+
 template <int OWT>
-__global__ __launch_bounds__(256) void conv3d_dgrad_s2_sp_kernel(
+__global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
     const __bf16* __restrict__ go, const __bf16* __restrict__ wb,
-    __bf16* __restrict__ dx, SpDims sd, int cls_off0, int cls_off1,
-    int cls_off2, int cls_off3, int cls_off4, int cls_off5, int cls_off6,
-    int cls_off7) {
+    __bf16* __restrict__ dx, SpDims sd) {
   constexpr int OHT = 128 / OWT;
-  constexpr int W2 = OWT + 4;        // OWT+1 used; padded
+  constexpr int W2 = OWT + 4;  // OWT+1 used; a row pitch of 4k positions
+                               // keeps the OWT-8 two-row fragments off
+                               // each other's banks
   constexpr int H2 = OHT + 1;
-  constexpr int MPW = (OWT * OHT) / 64;  // = 2
-  __shared__ __bf16 sG[32][2][H2][W2];
-  __shared__ unsigned short sKtab[32 * 8 + 8];
+  // the 4 waves tile the 128 m x 32 columns as 2 x 2: a wave owns 4
+  // m-fragments of ONE column fragment, so each 16-byte B load from L2
+  // feeds 4 MFMAs (2 m-fragments x 2 column fragments would load twice the
+  // B bytes per MFMA; every wave of a block reads the same WB rows)
+  constexpr int NCF = 1;           // column fragments per wave
+  constexpr int WCOL = 2 / NCF;    // waves side by side over the columns
+  constexpr int MPW = 2 * WCOL;    // m-fragments per wave
+  __shared__ __attribute__((aligned(16))) __bf16 sG[2 * H2 * W2 * 32];
 
-  const int cls = blockIdx.z;
-  const int a = (cls >> 2) & 1, b = (cls >> 1) & 1, c = cls & 1;
-  const int l2w = c, l2h = b;
-  const int T = 1 << (a + b + c);
-  const int cls_offs[8] = {cls_off0, cls_off1, cls_off2, cls_off3,
-                           cls_off4, cls_off5, cls_off6, cls_off7};
-  const int wb_cls = cls_offs[cls];
-
-  // dx sub-grid dims for this class
-  const int Da = (sd.TD - a + 1) >> 1;
-  const int Hb = (sd.TH - b + 1) >> 1;
-  const int Wc = (sd.TW - c + 1) >> 1;
+  // the CTILE 32 layout of conv3d_spatial_kernel: 64 B per position, 16-byte
+  // chunk ^= 2*bit2(w). Rows of a fragment are dense in w (or whole rows
+  // apart), the stride-1 case, so the four 16-lane groups of a 16-byte read
+  // land on distinct banks the same way.
+  auto slab_off = [](int p, int h, int w, int cl) -> int {
+    const int chunk = (cl >> 3) ^ (((w >> 2) & 1) << 1);
+    return ((p * H2 + h) * W2 + w) * 32 + chunk * 8 + (cl & 7);
+  };
 
   const int ncol0 = blockIdx.y * 32;
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int row = lane & 15, kg = lane >> 4;
+  const int wm = wave / WCOL, wj = wave % WCOL;
 
-  const int wtiles = (Wc + OWT - 1) / OWT;
-  const int htiles = (Hb + OHT - 1) / OHT;
-  const int64_t nchunks = (int64_t)sd.N * Da * htiles * wtiles;
-  if (blockIdx.x >= nchunks) return;
+  // sub-grid extents of the even classes; the odd ones are at most one
+  // shorter and are cut by the epilogue guards
+  const int Dq = (sd.TD + 1) >> 1;
+  const int Hq = (sd.TH + 1) >> 1;
+  const int Wq = (sd.TW + 1) >> 1;
+  const int wtiles = (Wq + OWT - 1) / OWT;
+  const int htiles = (Hq + OHT - 1) / OHT;
 
   int64_t t = blockIdx.x;
   const int wt = (int)(t % wtiles);
   t /= wtiles;
   const int ht = (int)(t % htiles);
   t /= htiles;
-  const int tdp = (int)(t % Da);     // id' (sub-grid d)
-  const int n = (int)(t / Da);
+  const int tdp = (int)(t % Dq);     // id' (sub-grid d)
+  const int n = (int)(t / Dq);
   const int oh0 = ht * OHT, ow0 = wt * OWT;
 
-  // k -> slab offset: k = co_l*T + r; r -> (dod, doh, dow) in {0,1}
-  for (int k = tid; k < 32 * T; k += 256) {
-    const int co_l = k >> (a + b + c);
-    const int r = k & (T - 1);
-    const int tw_i = r & ((1 << l2w) - 1);
-    const int th_i = (r >> l2w) & ((1 << l2h) - 1);
-    const int td_i = r >> (l2w + l2h);
-    const int dod = a ? (1 - td_i) : 0;
-    const int doh = b ? (1 - th_i) : 0;
-    const int dow = c ? (1 - tw_i) : 0;
-    sKtab[k] = (unsigned short)(((co_l * 2 + dod) * H2 + doh) * W2 + dow);
-  }
+  f32x4 acc[8][MPW][NCF];
+#pragma unroll
+  for (int cls = 0; cls < 8; ++cls)
+#pragma unroll
+    for (int i = 0; i < MPW; ++i)
+#pragma unroll
+      for (int j = 0; j < NCF; ++j) acc[cls][i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  f32x4 acc[MPW][2];
+  // A address = lanew[dow] + (shift plane/row, fragment) constants: the
+  // swizzle bit of w depends on (row, dow) only, fragments start 16 columns
+  // or whole rows apart
+  const int m_l = wm * (MPW * 16) + row;
+  int lanew[2];
 #pragma unroll
-  for (int i = 0; i < MPW; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  for (int dow = 0; dow < 2; ++dow)
+    lanew[dow] = slab_off(0, m_l / OWT, m_l % OWT + dow, kg * 8);
+  auto frag_off = [](int i) -> int {
+    return (((i * 16) / OWT) * W2 + (i * 16) % OWT) * 32;
+  };
+
+  // B: lane (col = row, kg) reads 8 consecutive local co of its ci row;
+  // tap slot g of co tile kt sits at (kt*27 + g)*32. WB has zero rows up to
+  // the next multiple of 32 ci, so a ragged column tile needs no check.
+  const int kts = (sd.KCH + 31) / 32;        // co tiles
+  const __bf16* wbl =
+      wb + (int64_t)(ncol0 + wj * NCF * 16 + row) * sd.Kpad + kg * 8;
 
   const int64_t OHW = (int64_t)sd.H * sd.W;  // go plane (input-side dims)
   const int64_t go_n = (int64_t)n * sd.KCH * sd.D * OHW;
-  const int kts = (sd.KCH + 31) / 32;        // co tiles
-  const int KT = 32 * T;                     // k per co tile (mult of 32)
+  constexpr int NV = OWT / 8;   // 8-column vectors per interior row
+  // a thread carries one 8-column vector of 4 adjacent co and stores 8
+  // interleaved 8-byte words, as the stride-1 staging does
+  constexpr int CG = 4, NCG = 32 / CG;
+  constexpr int NITEM = 2 * H2 * NV * NCG;
+  const bool wvec = (sd.W & 7) == 0;  // rows 16-byte aligned
 
   for (int kt = 0; kt < kts; ++kt) {
-    constexpr int NRMAX = 32 * 2 * H2;
     if (kt) __syncthreads();
-    else __syncthreads();  // ktab ready
-    for (int r = tid; r < NRMAX; r += 256) {
-      const int hrow = r % H2;
-      const int p = (r / H2) & 1;
-      const int co = r / (2 * H2);
-      const int od = tdp + p;                // dod in {0,1}
+    for (int it = tid; it < NITEM; it += 256) {
+      const int cg = it % NCG;
+      const int v = (it / NCG) % NV;
+      const int hrow = (it / (NCG * NV)) % H2;
+      const int p = it / (NCG * NV * H2);
+      const int od = tdp + p;
       const int oh = oh0 + hrow;
-      const int ch = kt * 32 + co;
-      __bf16* dst = &sG[co][p][hrow][0];
-      const bool row_ok = od < sd.D && oh < sd.H && ch < sd.KCH &&
-                          (a || p == 0);     // a==0 uses only plane 0
-      if (!row_ok) {
+      const int ow = ow0 + v * 8;
+      const bool row_ok = od < sd.D && oh < sd.H;
+      __bf16 tv[CG][8];
 #pragma unroll
-        for (int col = 0; col < W2; ++col) dst[col] = (__bf16)0.f;
-        continue;
-      }
-      const __bf16* src = go + go_n + ((int64_t)ch * sd.D + od) * OHW +
-                          (int64_t)oh * sd.W + ow0;
+      for (int cc = 0; cc < CG; ++cc) {
+        const int ch = kt * 32 + cg * CG + cc;
 #pragma unroll
-      for (int v = 0; v < OWT / 8; ++v) {
-        if (ow0 + v * 8 + 7 < sd.W) {
-          bf16x8 vec = *reinterpret_cast<const bf16x8*>(src + v * 8);
+        for (int j = 0; j < 8; ++j) tv[cc][j] = (__bf16)0.f;
+        if (row_ok && ch < sd.KCH) {
+          const __bf16* src = go + go_n + ((int64_t)ch * sd.D + od) * OHW +
+                              (int64_t)oh * sd.W;
+          if (wvec && ow + 8 <= sd.W) {
+            const bf16x8 vec = *reinterpret_cast<const bf16x8*>(src + ow);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) dst[v * 8 + j] = vec[j];
-        } else {
+            for (int j = 0; j < 8; ++j) tv[cc][j] = vec[j];
+          } else {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int ow = ow0 + v * 8 + j;
-            dst[v * 8 + j] = (ow < sd.W) ? src[v * 8 + j] : (__bf16)0.f;
+            for (int j = 0; j < 8; ++j)
+              if (ow + j < sd.W) tv[cc][j] = src[ow + j];
           }
         }
       }
-      {  // +1 tail column
-        const int ow = ow0 + OWT;
-        dst[OWT] = (ow < sd.W) ? src[OWT] : (__bf16)0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        bf16x4 o;
+#pragma unroll
+        for (int cc = 0; cc < CG; ++cc) o[cc] = tv[cc][j];
+        *reinterpret_cast<bf16x4*>(
+            sG + slab_off(p, hrow, v * 8 + j, cg * CG)) = o;
       }
+    }
+    // the +1 column: one element per (plane, row, co)
+    for (int it = tid; it < 2 * H2 * 32; it += 256) {
+      const int cl = it % 32;
+      const int hrow = (it / 32) % H2;
+      const int p = it / (32 * H2);
+      const int od = tdp + p;
+      const int oh = oh0 + hrow;
+      const int ow = ow0 + OWT;
+      const int ch = kt * 32 + cl;
+      __bf16 val = (__bf16)0.f;
+      if (od < sd.D && oh < sd.H && ow < sd.W && ch < sd.KCH)
+        val = go[go_n + ((int64_t)ch * sd.D + od) * OHW +
+                 (int64_t)oh * sd.W + ow];
+      sG[slab_off(p, hrow, OWT, cl)] = val;
     }
     __syncthreads();
 
-#pragma unroll 1
-    for (int ks = 0; ks < KT / 32; ++ks) {
+    // ---- 8 shifts; each feeds the classes that have a tap there --------
+    const __bf16* wbk = wbl + (int64_t)kt * (27 * 32);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int lk =
+          lanew[s & 1] + ((s >> 2) * H2 + ((s >> 1) & 1)) * W2 * 32;
       bf16x8 afrag[MPW];
-      {
-        const int kb = ks * 32 + kg * 8;
-        const u16x8 kt8 = *reinterpret_cast<const u16x8*>(&sKtab[kb]);
-        const __bf16* slab = &sG[0][0][0][0];
-#pragma unroll
-        for (int i = 0; i < MPW; ++i) {
-          const int m = (wave * MPW + i) * 16 + row;
-          const int base = (m / OWT) * W2 + (m % OWT);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            afrag[i][j] = slab[base + kt8[j]];
-        }
-      }
-      bf16x8 bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int col = ncol0 + i * 16 + row;
-        const int64_t off = (int64_t)col * sd.Kpad + wb_cls + kt * KT +
-                            ks * 32 + kg * 8;
-        bfrag[i] = (col < sd.NCOL)
-                       ? *reinterpret_cast<const bf16x8*>(wb + off)
-                       : bf16x8{};
-      }
 #pragma unroll
       for (int i = 0; i < MPW; ++i)
+        afrag[i] = *reinterpret_cast<const bf16x8*>(sG + lk + frag_off(i));
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
+      for (int cls = 0; cls < 8; ++cls) {
+        if (!s2_feeds(cls, s)) continue;
+        bf16x8 bfrag[NCF];
+#pragma unroll
+        for (int j = 0; j < NCF; ++j)
+          bfrag[j] = *reinterpret_cast<const bf16x8*>(
+              wbk + (int64_t)j * 16 * sd.Kpad + s2_slot(cls, s) * 32);
+#pragma unroll
+        for (int i = 0; i < MPW; ++i)
+#pragma unroll
+          for (int j = 0; j < NCF; ++j)
+            acc[cls][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag[i], bfrag[j], acc[cls][i][j], 0, 0, 0);
+      }
     }
   }
 
-  // epilogue: dx[n][ci][2*id'+a][2*ih'+b][2*iw'+c]
+  // ---- epilogue: dx[n][ci][2*id'+a][2*ih'+b][2*iw'+c] ------------------
+  // a lane's 4 consecutive m are 4 consecutive iw'; with both c classes
+  // they are 8 consecutive dx elements: one 16-byte store when the rows are
+  // 16-byte aligned (TW % 8 == 0; iw is a multiple of 8, so iw + 8 <= TW)
+  const bool pack8 = (sd.TW & 7) == 0;
   const int64_t THW = (int64_t)sd.TH * sd.TW;
   const int64_t dx_n = (int64_t)n * sd.NCOL * sd.TD * THW;
   const int ccol = lane & 15;
   const int crow0 = (lane >> 4) * 4;
 #pragma unroll
-  for (int i = 0; i < MPW; ++i) {
+  for (int ab = 0; ab < 4; ++ab) {
+    const int id = 2 * tdp + (ab >> 1);
+    if (id >= sd.TD) continue;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = ncol0 + j * 16 + ccol;
-      if (col >= sd.NCOL) continue;
+    for (int i = 0; i < MPW; ++i) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = (wave * MPW + i) * 16 + crow0 + r;
-        const int ihp = oh0 + m / OWT;
-        const int iwp = ow0 + m % OWT;
-        if (ihp < Hb && iwp < Wc)
-          dx[dx_n + ((int64_t)col * sd.TD + (2 * tdp + a)) * THW +
-             (int64_t)(2 * ihp + b) * sd.TW + (2 * iwp + c)] =
-              (__bf16)(acc[i][j][r]);
+      for (int j = 0; j < NCF; ++j) {
+        const int col = ncol0 + (wj * NCF + j) * 16 + ccol;
+        const int m = (wm * MPW + i) * 16 + crow0;
+        const int ih = 2 * (oh0 + m / OWT) + (ab & 1);
+        const int iw = 2 * (ow0 + m % OWT);
+        if (col >= sd.NCOL || ih >= sd.TH || iw >= sd.TW) continue;
+        __bf16* drow = dx + dx_n + ((int64_t)col * sd.TD + id) * THW +
+                       (int64_t)ih * sd.TW;
+        if (pack8) {
+          bf16x8 o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            o[2 * r] = (__bf16)acc[2 * ab][i][j][r];
+            o[2 * r + 1] = (__bf16)acc[2 * ab + 1][i][j][r];
+          }
+          *reinterpret_cast<bf16x8*>(drow + iw) = o;
+          continue;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (iw + 2 * r < sd.TW)
+            drow[iw + 2 * r] = (__bf16)acc[2 * ab][i][j][r];
+          if (iw + 2 * r + 1 < sd.TW)
+            drow[iw + 2 * r + 1] = (__bf16)acc[2 * ab + 1][i][j][r];
+        }
       }
     }
   }
+}
+
+// WB[ci][co tile][27 slots][32 local co], one launch straight from
+// w[Cout][Cin][27]: slot s2_slot(class, shift) holds tap s2_tap(class,
+// shift). co >= Cout and the rows [Cin, next multiple of 32) are zero.
+__global__ __launch_bounds__(256) void conv3d_dgrad_s2_prep_wb_kernel(
+    const __bf16* __restrict__ w, __bf16* __restrict__ wb, int cin, int cout,
+    int kpad, int total) {
+  constexpr S2TapTable tab = s2_tap_table();
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int ci = idx / kpad, k = idx - ci * kpad;
+  const int g = k >> 5;  // kt*27 + slot
+  const int co = (g / 27) * 32 + (k & 31);
+  __bf16 v = (__bf16)0.f;
+  if (ci < cin && co < cout)
+    v = w[((int64_t)co * cin + ci) * 27 + tab.tap[g % 27]];
+  wb[idx] = v;
 }
 
 torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
@@ -939,65 +1055,44 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
   CHECK_GPU(go);
   auto g = go.to(torch::kBFloat16).contiguous();
   auto wc = w.to(torch::kBFloat16).contiguous();
-  int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
+  const int Cout = (int)wc.size(0), Cin = (int)wc.size(1);
+  TORCH_CHECK(in_shape.size() == 5 && in_shape[0] == g.size(0) &&
+              in_shape[1] == Cin && g.size(1) == Cout,
+              "weight/grad/input shape mismatch");
   SpDims sd = make_spdims(g, Cin, (int)in_shape[2], (int)in_shape[3],
                           (int)in_shape[4]);
+  for (int i = 2; i < 5; ++i)
+    TORCH_CHECK(g.size(i) == (in_shape[i] + 1) / 2,
+                "go is not the stride-2 output of in_shape");
 
-  // per-class tap-gathered weights: WBc[ci][co*T + r]. The tap index
-  // tensors are compile-time constants — cached per device so no H2D
-  // copy happens on the hot path (pageable H2D is illegal inside a
-  // hipGraph capture).
-  auto w3 = wc.reshape({Cout, Cin, 27}).permute({1, 0, 2}).contiguous();
-  static std::vector<torch::Tensor> s_idx;       // [8], device-resident
-  static torch::Device s_dev = torch::kCPU;
-  if (s_idx.empty() || s_dev != wc.device()) {
-    s_idx.clear();
-    for (int cls = 0; cls < 8; ++cls) {
-      int a = (cls >> 2) & 1, b = (cls >> 1) & 1, c = cls & 1;
-      std::vector<int64_t> taps;
-      for (int td_i = 0; td_i < (a ? 2 : 1); ++td_i)
-        for (int th_i = 0; th_i < (b ? 2 : 1); ++th_i)
-          for (int tw_i = 0; tw_i < (c ? 2 : 1); ++tw_i) {
-            int kd = a ? td_i * 2 : 1;
-            int kh = b ? th_i * 2 : 1;
-            int kw = c ? tw_i * 2 : 1;
-            taps.push_back(kd * 9 + kh * 3 + kw);
-          }
-      s_idx.push_back(torch::tensor(taps, torch::TensorOptions()
-                                              .dtype(torch::kLong))
-                          .to(wc.device()));
-    }
-    s_dev = wc.device();
-  }
-  std::vector<torch::Tensor> blocks;
-  std::vector<int64_t> offs(8, 0);
-  int64_t cur = 0;
-  for (int cls = 0; cls < 8; ++cls) {
-    auto blk = w3.index_select(2, s_idx[cls]).reshape({Cin, -1});
-    offs[cls] = cur;
-    cur += blk.size(1);
-    blocks.push_back(blk);
-  }
-  auto wb = torch::cat(blocks, 1).contiguous();  // [Cin][Cout*27]
-  sd.Kpad = (int)wb.size(1);
+  const int kts = (Cout + 31) / 32;
+  const int kpad = kts * 27 * 32;
+  const int rows = (Cin + 31) / 32 * 32;
+  TORCH_CHECK((int64_t)rows * kpad < (int64_t)1 << 31, "WB too large");
+  auto wb = torch::empty({rows, (int64_t)kpad}, wc.options());
+  auto s = current_stream();
+  hipLaunchKernelGGL(conv3d_dgrad_s2_prep_wb_kernel,
+                     dim3((rows * kpad + 255) / 256), dim3(256), 0, s,
+                     reinterpret_cast<const __bf16*>(wc.data_ptr()),
+                     reinterpret_cast<__bf16*>(wb.data_ptr()), Cin, Cout,
+                     kpad, rows * kpad);
+  sd.Kpad = kpad;
 
   auto dx = torch::empty(in_shape, g.options());
-  int Wc = (sd.TW + 1) >> 1, Hb = (sd.TH + 1) >> 1, Da = (sd.TD + 1) >> 1;
-  int OWT = Wc % 32 == 0 ? 32 : (Wc % 16 == 0 ? 16 : 8);
-  int OHT = 128 / OWT;
-  int wtiles = (Wc + OWT - 1) / OWT;
-  int htiles = (Hb + OHT - 1) / OHT;
-  int64_t nchunks = (int64_t)sd.N * Da * htiles * wtiles;
-  dim3 grid((unsigned)nchunks, (Cin + 31) / 32, 8);
-  auto s = current_stream();
+  const int Wq = (sd.TW + 1) >> 1, Hq = (sd.TH + 1) >> 1;
+  const int Dq = (sd.TD + 1) >> 1;
+  const int OWT = Wq % 32 == 0 ? 32 : (Wq % 16 == 0 ? 16 : 8);
+  const int OHT = 128 / OWT;
+  const int wtiles = (Wq + OWT - 1) / OWT;
+  const int htiles = (Hq + OHT - 1) / OHT;
+  const int64_t nchunks = (int64_t)sd.N * Dq * htiles * wtiles;
+  TORCH_CHECK(nchunks < (int64_t)1 << 31, "grid too large");
+  dim3 grid((unsigned)nchunks, (Cin + 31) / 32);
   auto L = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, s,
                        reinterpret_cast<const __bf16*>(g.data_ptr()),
                        reinterpret_cast<const __bf16*>(wb.data_ptr()),
-                       reinterpret_cast<__bf16*>(dx.data_ptr()), sd,
-                       (int)offs[0], (int)offs[1], (int)offs[2],
-                       (int)offs[3], (int)offs[4], (int)offs[5],
-                       (int)offs[6], (int)offs[7]);
+                       reinterpret_cast<__bf16*>(dx.data_ptr()), sd);
   };
   if (OWT == 32) L(conv3d_dgrad_s2_sp_kernel<32>);
   else if (OWT == 16) L(conv3d_dgrad_s2_sp_kernel<16>);
