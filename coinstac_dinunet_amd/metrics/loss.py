@@ -1,4 +1,9 @@
-"""Segmentation losses (parity: reference metrics/loss.py:1-23)."""
+"""Segmentation losses (parity: reference metrics/loss.py:1-23).
+
+dice_loss_with_logits is the fused form for training: it takes the logits,
+runs as HIP kernels on GPU (ops/csrc/segloss.hip) and equals
+dice_loss_binary(sigmoid(logits), ...)."""
+from ..ops import dice_loss_with_logits  # noqa: F401  (re-export)
 
 
 def dice_loss_binary(outputs, target, beta=1.0, weights=None, eps=1e-5):

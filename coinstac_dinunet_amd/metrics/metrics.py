@@ -33,6 +33,11 @@ class COINNMetrics:
     def add(self, *args, **kw):
         raise NotImplementedError
 
+    def add_logits(self, logits, true):
+        """add() straight from the model's logits, for metrics that can
+        count without a materialised prediction tensor."""
+        raise NotImplementedError
+
     def accumulate(self, other):
         raise NotImplementedError
 
@@ -141,6 +146,27 @@ class Prf1a(COINNMetrics):
         self.tn += int((y_cases == 0).sum())
         self.fn += int((y_cases == 2).sum())
 
+    def add_logits(self, logits, true):
+        """Counts from logits, one fused pass on GPU (ops.seg_prf1a_counts /
+        ops.seg_confusion_matrix), no prediction tensor.
+
+        Same-shape logits: binary rule, pred = (logit > 0). [N, 2, ...]
+        logits against [N, ...] labels: argmax rule through the 2x2 matrix
+        (class 0 wins a tie)."""
+        from .. import ops
+        if logits.numel() == true.numel():
+            tp, fp, tn, fn = ops.seg_prf1a_counts(logits, true)
+        elif logits.dim() >= 2 and logits.shape[1] == 2 \
+                and logits.numel() == 2 * true.numel():
+            m = ops.seg_confusion_matrix(logits, true, 2).tolist()
+            (tn, fp), (fn, tp) = m
+        else:
+            raise ValueError(
+                f'Prf1a.add_logits: logits {tuple(logits.shape)} fit neither '
+                f'the binary nor the [N, 2, ...] form of true '
+                f'{tuple(true.shape)}')
+        self.tp += tp; self.fp += fp; self.tn += tn; self.fn += fn
+
     def accumulate(self, other):
         self.tp += other.tp
         self.fp += other.fp
@@ -229,6 +255,14 @@ class ConfusionMatrix(COINNMetrics):
         idx = true * self.num_classes + pred
         binc = torch.bincount(idx, minlength=self.num_classes ** 2)
         self.matrix += binc.reshape(self.num_classes, self.num_classes)
+
+    def add_logits(self, logits, true):
+        """add() from [N, K, ...] logits: argmax over the class planes with
+        the lowest index winning ties, fused with the histogram on GPU
+        (ops.seg_confusion_matrix)."""
+        from .. import ops
+        self.matrix += ops.seg_confusion_matrix(
+            logits, true, self.num_classes).cpu()
 
     def accumulate(self, other):
         self.matrix += other.matrix

@@ -11,6 +11,12 @@ convolution (not pooling) and upsampling is nearest-neighbor interp +
 conv — both stay inside the supported kernel family, no transposed-conv
 kernel needed. Skip connections go through safe_concat (center-crop) so
 odd input sizes work.
+
+Loss head: the model returns logits. Train on them directly with
+ops.dice_loss_with_logits (num_class=1) or ops.cross_entropy on the
+[N, C, D, H, W] logits (num_class > 1), and count with
+Prf1a.add_logits / ConfusionMatrix.add_logits — on GPU these are the fused
+kernels of ops/csrc/segloss.hip, with no probability or prediction tensor.
 """
 import os
 

@@ -14,6 +14,9 @@ runs through stock PyTorch — SURVEY.md §2.9):
   - flat gradient bucket pack / unpack            (K5/K7) — pack.hip
   - fused log_softmax + NLL loss fwd/bwd + argmax (K3/K16) — lsnll.hip
   - Prf1a confusion counts / KxK histogram        (K12/K13) — metrics.hip
+  - segmentation head from logits: binary soft-dice fwd/bwd, voxelwise
+    softmax cross-entropy fwd/bwd over [N, C, S...], tp/fp/tn/fn and
+    KxK confusion without a prediction tensor — segloss.hip
   - MFMA linear fwd (fused bias+ReLU) + dgrad + split-K wgrad (K2),
     parallel colsum — linear.hip
   - fused Gram-Schmidt for PowerSGD               (K8) — linear.hip
@@ -179,9 +182,44 @@ class _FusedLogSoftmaxNLL(torch.autograd.Function):
         return grad_logits, None
 
 
+class _VoxelCrossEntropy(torch.autograd.Function):
+    """Softmax cross-entropy over [N, C, S...] logits, mean over N*S voxels;
+    saves the fp32 log-sum-exp per voxel, not the log-probabilities."""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        C = require_native()
+        loss, lse = C.seg_ce_fwd(logits, target)
+        ctx.save_for_backward(logits, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        logits, target, lse = ctx.saved_tensors
+        return C.seg_ce_bwd(logits, target, lse, grad_out), None
+
+
+def _index_labels(target):
+    """Class-index labels the segmentation kernels read as they are: uint8,
+    bool or int64. Other integer widths are widened to int64."""
+    if target.dtype in (torch.uint8, torch.bool, torch.int64):
+        return target
+    if target.dtype.is_floating_point or target.dtype.is_complex:
+        raise TypeError(f'class-index labels must be integer or bool, '
+                        f'got {target.dtype}')
+    return target.long()
+
+
 def cross_entropy(logits, target):
-    """Fused log_softmax+NLL (mean reduction) — HIP on GPU, torch on CPU."""
+    """Fused log_softmax+NLL (mean reduction) — HIP on GPU, torch on CPU.
+
+    [B, C] logits run the classifier-head kernels (lsnll.hip); [N, C, S...]
+    logits with [N, S...] labels run the voxelwise kernels (segloss.hip),
+    mean over all N*S voxels. No ignore_index, no class weights."""
     if logits.is_cuda and native_available():
+        if logits.dim() > 2:
+            return _VoxelCrossEntropy.apply(logits, _index_labels(target))
         return _FusedLogSoftmaxNLL.apply(logits, target)
     return torch.nn.functional.cross_entropy(logits, target)
 
@@ -206,6 +244,100 @@ def confusion_matrix(pred, true, num_classes):
     """KxK confusion histogram on device (atomic scatter kernel)."""
     C = require_native()
     return C.confusion_matrix(pred, true, num_classes)
+
+
+# ---- segmentation head from logits (segloss.hip) ----------------------------
+class _DiceWithLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weights, beta, eps):
+        C = require_native()
+        loss, sums = C.seg_dice_fwd(logits, target, weights, beta, eps)
+        ctx.save_for_backward(logits, target, weights, sums)
+        ctx.beta, ctx.eps = beta, eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        logits, target, weights, sums = ctx.saved_tensors
+        g = C.seg_dice_bwd(logits, target, weights, sums, grad_out,
+                           ctx.beta, ctx.eps)
+        return g, None, None, None, None
+
+
+def dice_loss_with_logits(logits, target, beta=1.0, weights=None, eps=1e-5):
+    """Binary soft-dice loss (beta-F-score form) straight from logits:
+    dice_loss_binary(sigmoid(logits), target, beta, weights, eps).
+
+    On GPU one HIP pass accumulates the three sums and one pass writes the
+    gradient (in the logits' dtype), recomputing the sigmoid; no probability
+    tensor is kept and nothing synchronises the host. The gradient goes to
+    `logits` only. `target` is read as uint8, bool, int64, fp32 or the
+    logits' dtype (soft labels); `weights` as fp32. Other dtypes are
+    converted to fp32 first."""
+    if logits.is_cuda and native_available():
+        if target.dtype not in (torch.uint8, torch.bool, torch.int64,
+                                torch.float32, logits.dtype):
+            target = target.float()
+        if weights is not None:
+            weights = weights.detach().float()
+        return _DiceWithLogits.apply(logits, target.detach(), weights,
+                                     float(beta), float(eps))
+    from ..metrics.loss import dice_loss_binary
+    return dice_loss_binary(torch.sigmoid(logits), target, beta, weights, eps)
+
+
+def seg_prf1a_counts(logits, target):
+    """(tp, fp, tn, fn) as python ints from same-shape binary logits, with
+    pred = (logit > 0) and truth = (label != 0); one pass, no prediction
+    tensor, labels (integer or bool) read in their own dtype.
+
+    The rule is on the logit. It equals `sigmoid(x) > 0.5` except for
+    0 < x <~ 6e-8, where fp32 sigmoid rounds to exactly 0.5 and the
+    probability rule says negative (x = 1e-8: False there, True here).
+    +0.0 and -0.0 are both negative."""
+    logits = logits.detach()
+    target = _index_labels(target)
+    if logits.numel() != target.numel():
+        raise ValueError('logits and target must have the same numel')
+    if logits.is_cuda and native_available():
+        counts = require_native().seg_prf1a_counts(logits, target)
+        tp, fp, tn, fn = counts.tolist()   # the one D2H copy
+        return int(tp), int(fp), int(tn), int(fn)
+    p = (logits.reshape(-1) > 0).long()
+    y_cases = (target.reshape(-1) != 0).long() * 2 + p
+    return (int((y_cases == 3).sum()), int((y_cases == 1).sum()),
+            int((y_cases == 0).sum()), int((y_cases == 2).sum()))
+
+
+def argmax_lowest(logits):
+    """Argmax over dim 1 with the LOWEST index winning ties (torch.argmax
+    leaves the tie order unspecified) — the rule of seg_confusion_matrix."""
+    K = logits.shape[1]
+    idx = torch.arange(K, device=logits.device).view(
+        1, K, *([1] * (logits.dim() - 2)))
+    top = logits == logits.amax(dim=1, keepdim=True)
+    return torch.where(top, idx, K).amin(dim=1)
+
+
+def seg_confusion_matrix(logits, target, num_classes):
+    """int64 [K, K] matrix[true][pred] from [N, K, S...] logits and [N, S...]
+    labels: pred is the argmax over the class planes, lowest index on ties;
+    one pass, no prediction tensor. Labels outside [0, K) are dropped."""
+    logits = logits.detach()
+    target = _index_labels(target)
+    if logits.dim() < 2 or logits.shape[1] != num_classes:
+        raise ValueError(f'logits must be [N, {num_classes}, ...], '
+                         f'got {tuple(logits.shape)}')
+    if logits.is_cuda and native_available():
+        return require_native().seg_confusion_matrix(logits, target,
+                                                     num_classes)
+    pred = argmax_lowest(logits).reshape(-1)
+    true = target.reshape(-1).long()
+    keep = (true >= 0) & (true < num_classes)
+    binc = torch.bincount(true[keep] * num_classes + pred[keep],
+                          minlength=num_classes ** 2)
+    return binc.reshape(num_classes, num_classes)
 
 
 # ---- K2: MFMA GEMM (linear) -------------------------------------------------

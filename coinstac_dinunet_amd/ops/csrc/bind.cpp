@@ -31,6 +31,22 @@ torch::Tensor argmax_rows(torch::Tensor x);
 torch::Tensor prf1a_counts(torch::Tensor pred, torch::Tensor true_);
 torch::Tensor confusion_matrix(torch::Tensor pred, torch::Tensor true_,
                                int64_t num_classes);
+// segloss.hip
+std::vector<torch::Tensor> seg_dice_fwd(torch::Tensor logits,
+                                        torch::Tensor target,
+                                        c10::optional<torch::Tensor> weights,
+                                        double beta, double eps);
+torch::Tensor seg_dice_bwd(torch::Tensor logits, torch::Tensor target,
+                           c10::optional<torch::Tensor> weights,
+                           torch::Tensor sums, torch::Tensor grad_out,
+                           double beta, double eps);
+std::vector<torch::Tensor> seg_ce_fwd(torch::Tensor logits,
+                                      torch::Tensor target);
+torch::Tensor seg_ce_bwd(torch::Tensor logits, torch::Tensor target,
+                         torch::Tensor lse, torch::Tensor grad_out);
+torch::Tensor seg_prf1a_counts(torch::Tensor logits, torch::Tensor target);
+torch::Tensor seg_confusion_matrix(torch::Tensor logits, torch::Tensor target,
+                                   int64_t num_classes);
 // linear.hip
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor weight,
                          torch::Tensor bias, bool relu);
@@ -110,6 +126,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("argmax_rows", &argmax_rows);
   m.def("prf1a_counts", &prf1a_counts);
   m.def("confusion_matrix", &confusion_matrix);
+  m.def("seg_dice_fwd", &seg_dice_fwd);
+  m.def("seg_dice_bwd", &seg_dice_bwd);
+  m.def("seg_ce_fwd", &seg_ce_fwd);
+  m.def("seg_ce_bwd", &seg_ce_bwd);
+  m.def("seg_prf1a_counts", &seg_prf1a_counts);
+  m.def("seg_confusion_matrix", &seg_confusion_matrix);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_dgrad", &linear_dgrad);
   m.def("linear_wgrad", &linear_wgrad);
