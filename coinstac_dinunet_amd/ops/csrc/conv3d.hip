@@ -768,7 +768,7 @@ template <int OWT, int STRIDE, int CHUNK = 128, bool FUSE_BN = false,
 __global__ __launch_bounds__(256) void conv3d_wgrad_s1_kernel(
     const __bf16* __restrict__ x, const __bf16* __restrict__ go,
     float* __restrict__ dw, ConvDims cd, int64_t nchunks, int64_t zstride,
-    const float* __restrict__ bn_ab = nullptr) {
+    const float* __restrict__ bn_ab = nullptr, int tap_major = 0) {
   constexpr int OHT = CHUNK / OWT;
   constexpr int IW = STRIDE * OWT;
   constexpr int W2 = IW + (STRIDE == 1 ? 4 : 2);
@@ -904,6 +904,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_s1_kernel(
   }
 
   // ---- fold partials into dw[co][ci*27 + tap] -------------------------
+  // tap_major (the atomic fold of the host's default path): dw is
+  // [27][Cout][Cin], so the 16 ci of a fragment row are one 64-byte run per
+  // atomic instead of 16 cache lines 108 bytes apart
   const int K = cd.Cin * 27;
   float* out = SLICED ? dw + (int64_t)blockIdx.z * cd.Cout * K : dw;
   const int ccol = lane & 15;          // ci col within fragment
@@ -917,6 +920,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_s1_kernel(
       if (co < cd.Cout && ci < cd.Cin) {
         if (SLICED)
           out[(int64_t)co * K + ci * 27 + tp] = acc[tp][r];
+        else if (tap_major)
+          atomicAdd(&out[((int64_t)tp * cd.Cout + co) * cd.Cin + ci],
+                    acc[tp][r]);
         else
           atomicAdd(&out[(int64_t)co * K + ci * 27 + tp], acc[tp][r]);
       }
@@ -940,7 +946,7 @@ template <int OWT, int CHUNK = 128, bool FUSE_BN = false, bool SLICED = false>
 __global__ __launch_bounds__(256) void conv3d_wgrad_s1_pf_kernel(
     const __bf16* __restrict__ x, const __bf16* __restrict__ go,
     float* __restrict__ dw, ConvDims cd, int64_t nchunks, int64_t zstride,
-    const float* __restrict__ bn_ab = nullptr) {
+    const float* __restrict__ bn_ab = nullptr, int tap_major = 0) {
   constexpr int OHT = CHUNK / OWT;
   constexpr int IW = OWT;
   constexpr int W2 = IW + 4;
@@ -1151,6 +1157,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_s1_pf_kernel(
       if (co < cd.Cout && ci < cd.Cin) {
         if (SLICED)
           out[(int64_t)co * K + ci * 27 + tp] = acc[tp][r];
+        else if (tap_major)
+          atomicAdd(&out[((int64_t)tp * cd.Cout + co) * cd.Cin + ci],
+                    acc[tp][r]);
         else
           atomicAdd(&out[(int64_t)co * K + ci * 27 + tp], acc[tp][r]);
       }
@@ -1511,6 +1520,12 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
     const bool sliced = (variant == 0) && zstride >= 32 &&
                         (int64_t)zstride * cd.Cout * K * 4 <=
                             (int64_t)512 * 1024 * 1024;
+    // the atomic fold accumulates tap-major, [27][Cout][Cin], and one
+    // permuting copy restores [Cout][Cin*27]: with taps innermost a wave's
+    // atomic touched 64 cache lines, and at the d8-class layers (z-stride 8
+    // and 16, 14 M atomics) the fold was two thirds of the launch
+    // (profiles/smallplane_ab.md)
+    const bool tap_major = !sliced && variant == 0;
     torch::Tensor part;
     float* outp;
     if (sliced) {
@@ -1519,6 +1534,7 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
       outp = part.data_ptr<float>();
     } else {
       zero_dw();
+      if (tap_major) dw = dw.view({27, (int64_t)cd.Cout, (int64_t)cd.Cin});
       outp = dw.data_ptr<float>();
     }
     dim3 grid(co_t, ci_t, (unsigned)zstride);
@@ -1551,7 +1567,7 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
                   kern, grid, dim3(256), 0, current_stream(),
                   reinterpret_cast<const __bf16*>(xc.data_ptr()),
                   reinterpret_cast<const __bf16*>(g.data_ptr()), outp, cd,
-                  nchunks, zstride, abp);
+                  nchunks, zstride, abp, tap_major ? 1 : 0);
             };
             if constexpr (!s2_v && !(owt_v == 8 && ch_v == 128))
               launch(conv3d_wgrad_s1_pf_kernel<owt_v, ch_v,
@@ -1566,6 +1582,7 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
       });
     });
     if (sliced) dw = part.sum(0);
+    if (tap_major) dw = dw.permute({1, 2, 0}).contiguous();
     return dw.view({cd.Cout, cd.Cin, 3, 3, 3});
   }
 

@@ -44,7 +44,12 @@ struct SpDims {
 // Waves per SIMD the register allocation must leave room for. The
 // small-slab chunk-64 instances are not LDS-limited, and the unrolled tap
 // loop would otherwise trade their occupancy for hoisted loads.
-constexpr int sp_min_waves(int ctile, int chunk, int ncolt, bool fuse_bn) {
+constexpr int sp_min_waves(int ctile, int chunk, int ncolt, bool fuse_bn,
+                           int dt) {
+  // depth-blocked: DT * NCOLT/16 accumulator fragments (64 registers on the
+  // kept instances) next to the staging registers; the 46-49 KB slab holds
+  // a CU to 3 blocks anyway
+  if (dt > 1) return 2;
   if (ctile < 16 || chunk != 64) return 1;
   if (ncolt == 128 || fuse_bn) return 4;
   return ncolt == 32 ? 6 : 5;
@@ -59,11 +64,18 @@ constexpr int sp_min_waves(int ctile, int chunk, int ncolt, bool fuse_bn) {
 // the written elements into stats[hash_slice][NCOL][2] — the NEXT
 // block's BN statistics come for free (no standalone bn_reduce pass).
 // Hash slices (blockIdx.x & 63) spread the atomics.
+// DT > 1 (whole-plane chunk-64 tiles, TW == 8 and TH <= 8): a block covers
+// DT consecutive output depth planes from one slab of (DT-1)*STRIDE + 3
+// input planes. Fragment i of a wave is the wave's 16 rows of plane td + i,
+// a whole-plane stride away in the slab, so each B load feeds DT MFMAs and
+// an input plane is staged (DT+2)/DT times instead of 3. The tile covers
+// the plane, so the halo rows and columns are padding: zeroed once, never
+// staged. K order per output element is that of DT = 1.
 template <int OWT, int STRIDE, int CTILE,
           int CHUNK = (STRIDE == 1 ? 256 : 128), bool FUSE_BN = false,
-          int SMODE = 0, int NCOLT = 32>
+          int SMODE = 0, int NCOLT = 32, int DT = 1>
 __global__ __launch_bounds__(
-    256, sp_min_waves(CTILE, CHUNK, NCOLT, FUSE_BN))
+    256, sp_min_waves(CTILE, CHUNK, NCOLT, FUSE_BN, DT))
 void conv3d_spatial_kernel(
     const __bf16* __restrict__ in, const __bf16* __restrict__ wb,
     __bf16* __restrict__ out, SpDims sd, int64_t nchunks,
@@ -73,8 +85,11 @@ void conv3d_spatial_kernel(
   constexpr int IW = STRIDE * OWT;                  // staged interior width
   constexpr int W2 = IW + (STRIDE == 1 ? 4 : 2);
   constexpr int H2 = STRIDE * (OHT - 1) + 3;
-  constexpr int MPW = CHUNK / 64;                   // m-frags per wave
+  constexpr int MPW = DT * CHUNK / 64;              // m-frags per wave
   static_assert(MPW >= 1, "chunk too small");
+  static_assert(DT == 1 || (CTILE >= 16 && OWT == 8 && CHUNK == 64),
+                "depth blocking: whole-plane chunk-64 tiles only");
+  constexpr int PD = (DT - 1) * STRIDE + 3;         // staged depth planes
   constexpr int KT_PAD = ((CTILE * 27 + 31) / 32) * 32;
   constexpr int NCF = NCOLT / 16;  // ncol fragments per wave
   constexpr bool CL = CTILE >= 16;  // channel-innermost slab, b128 A reads
@@ -82,7 +97,7 @@ void conv3d_spatial_kernel(
                 "channel-innermost tiles: 32 (stride 1) or 16");
   static_assert(!CL || (CHUNK / 4) % OWT == 0 || OWT == 8,
                 "a wave's fragments must start on a tile row");
-  __shared__ __attribute__((aligned(16))) __bf16 sXf[CTILE * 3 * H2 * W2];
+  __shared__ __attribute__((aligned(16))) __bf16 sXf[CTILE * PD * H2 * W2];
   __shared__ unsigned short sKtab[CL ? 8 : KT_PAD + 8];
   auto sX = reinterpret_cast<__bf16(*)[3][H2][W2]>(sXf);  // !CL view
 
@@ -99,8 +114,9 @@ void conv3d_spatial_kernel(
   t /= wtiles;
   const int ht = (int)(t % htiles);
   t /= htiles;
-  const int td = (int)(t % sd.TD);
-  const int n = (int)(t / sd.TD);
+  const int dgroups = (sd.TD + DT - 1) / DT;
+  const int td = (int)(t % dgroups) * DT;  // first output plane
+  const int n = (int)(t / dgroups);
   const int oh0 = ht * OHT, ow0 = wt * OWT;
 
   // k -> slab element offset (pad entries -> 0: their weights are zero)
@@ -144,13 +160,14 @@ void conv3d_spatial_kernel(
     // A address = lanew[c] + (fragment, tap-plane) constants: the swizzle
     // bits of w depend on (row, c) only, fragments start 16 or 32 columns
     // apart and tap planes whole rows apart
-    const int m_l = wave * (MPW * 16) + row;
+    const int m_l = (DT > 1 ? wave * 16 : wave * (MPW * 16)) + row;
     int lanew[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       lanew[c] = slab_off(0, STRIDE * (m_l / OWT), STRIDE * (m_l % OWT) + c,
                           (CTILE == 32 ? kg : (kg & 1)) * 8);
     auto frag_off = [](int i) -> int {
+      if (DT > 1) return i * STRIDE * H2 * W2 * CTILE;
       return (STRIDE * ((i * 16) / OWT) * W2 + STRIDE * ((i * 16) % OWT)) *
              CTILE;
     };
@@ -176,20 +193,31 @@ void conv3d_spatial_kernel(
     // stores 8 interleaved CG-channel words (lanes run over channel group,
     // then column vector: 2- to 4-way conflicted stores, but the row-
     // interleaved conflict-free order lost, profiles/spatial_b128_ab.md)
-    constexpr int CG = (3 * H2 * NV * (CTILE / 8) >= 256) ? 8 : 4;
+    // DT > 1 stages the STRIDE*8 interior rows only (slab rows 1..)
+    constexpr int HR = DT > 1 ? STRIDE * 8 : H2;
+    constexpr int HR0 = DT > 1 ? 1 : 0;
+    constexpr int CG = (PD * HR * NV * (CTILE / 8) >= 256) ? 8 : 4;
     constexpr int NCG = CTILE / CG;
-    constexpr int NITEM = 3 * H2 * NV * NCG;
+    constexpr int NITEM = PD * HR * NV * NCG;
     constexpr int NHALO = STRIDE == 1 ? 2 : 1;  // halo columns the taps read
     const int iw0 = STRIDE * ow0;
     const bool wvec = (sd.W & 7) == 0;  // rows 16-byte aligned
+
+    if constexpr (DT > 1) {
+      // the halo is conv padding (zero AFTER the BN transform): written
+      // here once, the interior stores below never touch it
+      for (int it = tid; it < CTILE * PD * H2 * W2 / 8; it += 256)
+        reinterpret_cast<bf16x8*>(sXf)[it] = bf16x8{};
+      __syncthreads();
+    }
 
     for (int kt = 0; kt < kts; ++kt) {
       if (kt) __syncthreads();
       for (int it = tid; it < NITEM; it += 256) {
         const int cg = it % NCG;
         const int v = (it / NCG) % NV;
-        const int hrow = (it / (NCG * NV)) % H2;
-        const int a = it / (NCG * NV * H2);
+        const int hrow = HR0 + (it / (NCG * NV)) % HR;
+        const int a = it / (NCG * NV * HR);
         const int id = STRIDE * td - 1 + a;
         const int ih = STRIDE * oh0 - 1 + hrow;
         const int iw = iw0 + v * 8;
@@ -238,7 +266,7 @@ void conv3d_spatial_kernel(
         }
       }
       // halo columns: one element per (plane, row, side, channel)
-      for (int it = tid; it < 3 * H2 * NHALO * CTILE; it += 256) {
+      for (int it = tid; DT == 1 && it < 3 * H2 * NHALO * CTILE; it += 256) {
         const int cl = it % CTILE;
         const int side = (it / CTILE) % NHALO;
         const int hrow = (it / (CTILE * NHALO)) % H2;
@@ -306,6 +334,9 @@ void conv3d_spatial_kernel(
 #pragma unroll
           for (int j = 0; j < NCF; ++j) bcur[j] = bnext[j];
         }
+        // keep the unrolled loop's B loads in their own k-step: hoisted
+        // over the DT * NCF accumulator fragments they spill
+        if constexpr (DT > 1) __builtin_amdgcn_sched_barrier(0);
       }
     }
   } else {
@@ -403,12 +434,17 @@ void conv3d_spatial_kernel(
   static_assert(NCF <= 8, "stats buffers sized for NCF <= 8");
 #pragma unroll
   for (int i = 0; i < MPW; ++i) {
+    // depth-blocked: fragment i is the wave's 16 rows of plane td + i;
+    // planes of a ragged last group past TD are neither stored nor counted
+    const int tdi = DT > 1 ? td + i : td;
+    const int mw = DT > 1 ? wave * 16 : (wave * MPW + i) * 16;
+    if (tdi >= sd.TD) continue;
 #pragma unroll
     for (int j = 0; j < NCF; ++j) {
       const int col = ncol0 + j * 16 + ccol;
       if (col >= sd.NCOL) continue;
       if (pack4) {
-        const int m = (wave * MPW + i) * 16 + crow0;
+        const int m = mw + crow0;
         const int oh = oh0 + m / OWT;
         const int ow = ow0 + m % OWT;
         if (oh < sd.TH && ow < sd.TW) {  // ow % 4 == 0: ow + 3 < TW too
@@ -423,19 +459,19 @@ void conv3d_spatial_kernel(
             }
           }
           *reinterpret_cast<bf16x4*>(
-              out + out_n + ((int64_t)col * sd.TD + td) * THW +
+              out + out_n + ((int64_t)col * sd.TD + tdi) * THW +
               (int64_t)oh * sd.TW + ow) = o;
         }
         continue;
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int m = (wave * MPW + i) * 16 + crow0 + r;
+        const int m = mw + crow0 + r;
         const int oh = oh0 + m / OWT;
         const int ow = ow0 + m % OWT;
         if (oh < sd.TH && ow < sd.TW) {
           const float v = acc[i][j][r];
-          const int64_t off = out_n + ((int64_t)col * sd.TD + td) * THW +
+          const int64_t off = out_n + ((int64_t)col * sd.TD + tdi) * THW +
                               (int64_t)oh * sd.TW + ow;
           out[off] = (__bf16)v;
           if (SMODE == 1) {
@@ -511,6 +547,7 @@ enum SpMode {
 struct SpatialPlan {
   int owt, chunk, ctile, ncolt;  // template arguments of the instance
   int gcolt;                     // column tile the grid's y extent is cut by
+  int dt;                        // output depth planes per block
 };
 
 static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
@@ -519,6 +556,7 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
   p.chunk = stride == 1 ? 256 : 128;
   p.ctile = mode == SP_CTILE1 ? 1 : (stride == 1 ? 32 : 16);
   p.ncolt = p.gcolt = 32;
+  p.dt = 1;
   const bool fused = mode == SP_FUSED || mode == SP_FUSED_STATS;
   // thin-channel large-plane stride-1 layers (L2-class): chunk 512 at
   // CTILE 16 doubles the m that amortizes each staged slab — dgrad 36.2 vs
@@ -547,6 +585,15 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
     // (37.7 vs 38.2 ms/step flagship) — slab re-reads drop 4x vs 32-col
     if (sd.NCOL >= 64 && mode != SP_CTILE1)
       p.gcolt = sd.NCOL >= 128 ? 128 : 64;
+    // one tile is the whole output plane (d8-class forwards): depth-blocked
+    // instances, one (DT, column tile) per stride whatever NCOL is — 4
+    // planes x 64 columns at stride 1 (the 6-plane slab is 46 KB), 2 x 128
+    // at stride 2 (49 KB; DT 4 does not fit). Swept on MI355X,
+    // profiles/smallplane_ab.md.
+    if ((mode == SP_PLAIN || fused) && sd.TW == 8 && sd.TH <= 8) {
+      p.dt = stride == 1 ? 4 : 2;
+      p.gcolt = stride == 1 ? 64 : 128;
+    }
   }
   p.ncolt = p.gcolt;
   // KNOWN DEFECT, kept as it was (docs/NEXT.md, "Under-covered column
@@ -604,22 +651,24 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
   const int oht = p.chunk / p.owt;
   const int wtiles = (sd.TW + p.owt - 1) / p.owt;
   const int htiles = (sd.TH + oht - 1) / oht;
-  const int64_t nchunks = (int64_t)sd.N * sd.TD * htiles * wtiles;
+  const int64_t nchunks =
+      (int64_t)sd.N * ((sd.TD + p.dt - 1) / p.dt) * htiles * wtiles;
   dim3 grid((unsigned)nchunks, (sd.NCOL + p.gcolt - 1) / p.gcolt);
   auto s = current_stream();
   const __bf16* ip = reinterpret_cast<const __bf16*>(in.data_ptr());
   const __bf16* wp = reinterpret_cast<const __bf16*>(wb.data_ptr());
   __bf16* op = reinterpret_cast<__bf16*>(out.data_ptr());
-  // launches instance <OWT, STRIDE, CTILE, CHUNK, FUSE_BN, SMODE, NCOLT>
+  // launches instance <OWT, STRIDE, CTILE, CHUNK, FUSE_BN, SMODE, NCOLT, DT>
   auto K = [&](auto owt, auto st, auto ct, auto ch, auto fz, auto sm,
-               auto nc) {
+               auto nc, auto dt) {
     hipLaunchKernelGGL(
         (conv3d_spatial_kernel<decltype(owt)::value, decltype(st)::value,
                                decltype(ct)::value, decltype(ch)::value,
                                decltype(fz)::value, decltype(sm)::value,
-                               decltype(nc)::value>),
+                               decltype(nc)::value, decltype(dt)::value>),
         grid, dim3(256), 0, s, ip, wp, op, sd, nchunks, bn_ab, stats);
   };
+  const IntC<1> dt1{};
   auto with_owt = [&](auto f) {
     if (p.owt == 32) f(IntC<32>{});
     else if (p.owt == 16) f(IntC<16>{});
@@ -642,26 +691,39 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
     // whole 27-tap K, slab is [1][3][H2][W2]; plain epilogue only
     if (p.chunk == 64)
       K(IntC<8>{}, IntC<1>{}, IntC<1>{}, IntC<64>{}, plain, IntC<0>{},
-        IntC<32>{});
+        IntC<32>{}, dt1);
     else
       with_owt([&](auto owt) {
         K(owt, IntC<1>{}, IntC<1>{}, IntC<256>{}, plain, IntC<0>{},
-          IntC<32>{});
+          IntC<32>{}, dt1);
       });
   } else if (p.chunk == 512) {
     // plain (dgrad) and fused+stats (fwd) only
     dispatch_bool(mode == SP_FUSED_STATS, [&](auto fs) {
       K(IntC<32>{}, IntC<1>{}, IntC<16>{}, IntC<512>{}, fs,
-        IntC<decltype(fs)::value ? 1 : 0>{}, IntC<32>{});
+        IntC<decltype(fs)::value ? 1 : 0>{}, IntC<32>{}, dt1);
+    });
+  } else if (p.chunk == 64 && p.dt > 1) {
+    // whole-plane depth-blocked: every epilogue, one (DT, NCOLT) per stride
+    TORCH_CHECK(stride == 1 ? (p.dt == 4 && p.ncolt == 64)
+                            : (p.dt == 2 && p.ncolt == 128),
+                "no depth-blocked instance for this plan");
+    with_epilogue([&](auto fz, auto sm) {
+      if (stride == 1)
+        K(IntC<8>{}, IntC<1>{}, IntC<32>{}, IntC<64>{}, fz, sm, IntC<64>{},
+          IntC<4>{});
+      else
+        K(IntC<8>{}, IntC<2>{}, IntC<16>{}, IntC<64>{}, fz, sm, IntC<128>{},
+          IntC<2>{});
     });
   } else if (p.chunk == 64) {
     // every epilogue x {32, 64, 128} columns x stride
     with_epilogue([&](auto fz, auto sm) {
       with_ncolt([&](auto nc) {
         if (stride == 1)
-          K(IntC<8>{}, IntC<1>{}, IntC<32>{}, IntC<64>{}, fz, sm, nc);
+          K(IntC<8>{}, IntC<1>{}, IntC<32>{}, IntC<64>{}, fz, sm, nc, dt1);
         else
-          K(IntC<8>{}, IntC<2>{}, IntC<16>{}, IntC<64>{}, fz, sm, nc);
+          K(IntC<8>{}, IntC<2>{}, IntC<16>{}, IntC<64>{}, fz, sm, nc, dt1);
       });
     });
   } else if (stride == 2) {
@@ -669,7 +731,7 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
     with_epilogue([&](auto fz, auto sm) {
       with_ncolt([&](auto nc) {
         with_owt([&](auto owt) {
-          K(owt, IntC<2>{}, IntC<16>{}, IntC<128>{}, fz, sm, nc);
+          K(owt, IntC<2>{}, IntC<16>{}, IntC<128>{}, fz, sm, nc, dt1);
         });
       });
     });
@@ -678,12 +740,12 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
     // docs/KERNELS.md)
     with_owt([&](auto owt) {
       K(owt, IntC<1>{}, IntC<32>{}, IntC<256>{}, plain, IntC<0>{},
-        IntC<64>{});
+        IntC<64>{}, dt1);
     });
   } else {
     with_epilogue([&](auto fz, auto sm) {
       with_owt([&](auto owt) {
-        K(owt, IntC<1>{}, IntC<32>{}, IntC<256>{}, fz, sm, IntC<32>{});
+        K(owt, IntC<1>{}, IntC<32>{}, IntC<256>{}, fz, sm, IntC<32>{}, dt1);
       });
     });
   }
