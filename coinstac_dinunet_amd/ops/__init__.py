@@ -9,7 +9,8 @@ runs through stock PyTorch — SURVEY.md §2.9):
   - Conv2d fwd/dgrad/wgrad (ResNet): igemm (3x3 + 7x7 stem), spatial
     slab, tap-reuse + split-K wgrad, parity s2 dgrad — conv2d.hip
   - pointwise 1x1 convs as batched MFMA GEMMs     — pointwise.hip
-  - fused BatchNorm(+ReLU[+residual]) fwd/bwd, stats-only — bnorm.hip
+  - fused BatchNorm(+ReLU[+residual]) fwd/bwd, stats-only, one-launch
+    finalize of the conv-epilogue partials          — bnorm.hip
   - single-launch multi-tensor Adam / SGD         (K4) — adam.hip
   - flat gradient bucket pack / unpack            (K5/K7) — pack.hip
   - fused log_softmax + NLL loss fwd/bwd + argmax (K3/K16) — lsnll.hip

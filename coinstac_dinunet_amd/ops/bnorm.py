@@ -40,6 +40,36 @@ def update_running_stats(running_mean, running_var, mean, var, n, factor):
         running_var.mul_(1 - factor).add_(unbiased, alpha=factor)
 
 
+def _native_running(t):
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def bn_finalize_attached(x, bn, factor):
+    """(mean, var, mean_rstd, ab) of `x` from the epilogue partials its
+    producing conv attached (x._coinn_bn_stats), in ONE launch: folds the
+    slices, forms ab = (gamma*rstd, beta - mean*gamma*rstd) for the
+    normalize-on-load consumers and applies `factor` (from
+    bn_momentum_step; None = no update) to bn's running buffers."""
+    C = require_native()
+    per_ch = x.numel() // x.size(1)
+    rm, rv = bn.running_mean, bn.running_var
+    update = factor is not None and rm is not None
+    fused = update and _native_running(rm) and _native_running(rv)
+    with torch.no_grad():
+        mean, var, mean_rstd, ab = C.bn_finalize(
+            x._coinn_bn_stats, per_ch, bn.eps, bn.weight, bn.bias,
+            rm if fused else None, rv if fused else None,
+            factor if fused else 0.0)
+        if update and not fused:
+            update_running_stats(rm, rv, mean, var, per_ch, factor)
+    return mean, var, mean_rstd, ab
+
+
+def has_attached_stats(x):
+    stats = getattr(x, '_coinn_bn_stats', None)
+    return stats is not None and stats.numel() > 0
+
+
 def _bn3d_backward(ctx, dy):
     """Shared backward of _BN3dFn / _BN3dPreFn: grads for (x, gamma, beta);
     every further forward argument is non-differentiable."""
@@ -78,14 +108,10 @@ class _OpsBNMixin:
             return F.relu(y, inplace=True) if self.relu else y
         if self.training:
             factor = bn_momentum_step(self)
-            if getattr(x, '_coinn_bn_stats', None) is not None:
-                # stats came free from the producing conv's epilogue
-                from .conv import bn_stats_of
-                # pass x itself: .to() would drop the attached stats
-                mean, var, mean_rstd = bn_stats_of(x, self.eps)
-                update_running_stats(self.running_mean, self.running_var,
-                                     mean, var, x.numel() // x.size(1),
-                                     factor)
+            if has_attached_stats(x):
+                # stats came free from the producing conv's epilogue; pass
+                # x itself: .to() would drop the attached stats
+                _, _, mean_rstd, _ = bn_finalize_attached(x, self, factor)
                 return _BN3dPreFn.apply(x, self.weight, self.bias,
                                         mean_rstd, self.relu)
             return _BN3dFn.apply(x, self.weight, self.bias,

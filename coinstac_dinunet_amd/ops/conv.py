@@ -17,7 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import native_available, require_native
-from .bnorm import (OpsBatchNorm2d, OpsBatchNorm3d, bn_momentum_step,
+from .bnorm import (OpsBatchNorm2d, OpsBatchNorm3d, bn_finalize_attached,
+                    bn_momentum_step, has_attached_stats,
                     update_running_stats)
 
 # Double-buffered stride-1 wgrad: numerically validated, measured WORSE
@@ -130,18 +131,19 @@ class _ConvBNFn(torch.autograd.Function):
     kernels re-apply it on load in backward. Per BN layer this deletes one
     full activation write + one full read vs the separate normalize pass
     (VERDICT r1 item 3). mean_rstd enters as a non-differentiable constant:
-    bn3d_bwd's dx formula accounts for the statistic dependence.
+    bn3d_bwd's dx formula accounts for the statistic dependence. `ab` comes
+    ready from the one-launch finalize when the input carries epilogue
+    partials; only without it is the affine formed here.
     """
 
     @staticmethod
-    def forward(ctx, x_raw, gamma, beta, mean_rstd, weight, bias, stride):
+    def forward(ctx, x_raw, gamma, beta, mean_rstd, weight, bias, stride,
+                ab=None):
         C = require_native()
         xb = x_raw.to(torch.bfloat16)
         wb = weight.to(torch.bfloat16)
-        with torch.no_grad():
-            a = gamma.float() * mean_rstd[:, 1]
-            b = beta.float() - mean_rstd[:, 0] * a
-            ab = torch.stack([a, b], 1).contiguous()
+        if ab is None:
+            ab = _affine_ab(gamma, beta, mean_rstd)
         stats = None
         if route_fused_fwd3d(xb.size(1), xb.size(3), xb.size(4),
                              stride) == 'spatial':
@@ -181,7 +183,7 @@ class _ConvBNFn(torch.autograd.Function):
                                    and ctx.needs_input_grad[5]) else None
         dx, dgamma, dbeta = C.bn3d_bwd(dz, xb, mean_rstd, gamma, beta, True)
         return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
-                dbeta.to(beta.dtype), None, gw, gb, None)
+                dbeta.to(beta.dtype), None, gw, gb, None, None)
 
 
 def conv_bn3d(x_raw, bn, conv):
@@ -191,29 +193,43 @@ def conv_bn3d(x_raw, bn, conv):
     the 3x3x3/pad-1/stride-{1,2} family. Handles running-stat updates with
     the exact semantics of the unfused module.
     """
-    out, stats = _ConvBNFn.apply(x_raw, bn.weight, bn.bias,
-                                 _bn_mean_rstd(x_raw, bn),
+    mean_rstd, ab = _bn_mean_rstd(x_raw, bn)
+    out, stats = _ConvBNFn.apply(x_raw, bn.weight, bn.bias, mean_rstd,
                                  conv.weight, conv.bias,
-                                 int(conv.stride[0]))
+                                 int(conv.stride[0]), ab)
     if stats.numel() > 0:
         out._coinn_bn_stats = stats
     return out
 
 
+def _affine_ab(gamma, beta, mean_rstd):
+    """[C][2] (a, b) of the normalize-on-load affine z = a*x + b."""
+    with torch.no_grad():
+        a = gamma.float() * mean_rstd[:, 1]
+        b = beta.float() - mean_rstd[:, 0] * a
+        return torch.stack([a, b], 1).contiguous()
+
+
 def _bn_mean_rstd(x_raw, bn):
-    """[C][2] (mean, rstd) that `bn` normalizes x_raw with — batch stats
-    in training (running stats updated exactly as the unfused module
-    would), running stats in eval."""
+    """([C][2] (mean, rstd), [C][2] (a, b) or None) that `bn` normalizes
+    x_raw with — batch stats in training (running stats updated exactly as
+    the unfused module would), running stats in eval. With epilogue
+    partials attached to x_raw the training form is one native launch and
+    brings the affine along; otherwise ab is None."""
     xb = x_raw if x_raw.dtype == torch.bfloat16 \
         else x_raw.to(torch.bfloat16)
     if bn.training:
+        if has_attached_stats(xb):
+            _, _, mean_rstd, ab = bn_finalize_attached(
+                xb, bn, bn_momentum_step(bn))
+            return mean_rstd, ab
         mean, var, mean_rstd = bn_stats_of(xb, bn.eps)
         update_running_stats(bn.running_mean, bn.running_var, mean, var,
                              xb.numel() // xb.size(1), bn_momentum_step(bn))
-        return mean_rstd
+        return mean_rstd, None
     mean = bn.running_mean.float()
     rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-    return torch.stack([mean, rstd], 1).contiguous()
+    return torch.stack([mean, rstd], 1).contiguous(), None
 
 
 def bn_stats_of(xb, eps):
@@ -237,14 +253,13 @@ class _ConvBN2dFn(torch.autograd.Function):
     conv's input load (ResNet BasicBlock's bn1 -> conv2 pair)."""
 
     @staticmethod
-    def forward(ctx, x_raw, gamma, beta, mean_rstd, weight, stride):
+    def forward(ctx, x_raw, gamma, beta, mean_rstd, weight, stride,
+                ab=None):
         C = require_native()
         xb = x_raw.to(torch.bfloat16)
         wb = weight.to(torch.bfloat16)
-        with torch.no_grad():
-            a = gamma.float() * mean_rstd[:, 1]
-            b = beta.float() - mean_rstd[:, 0] * a
-            ab = torch.stack([a, b], 1).contiguous()
+        if ab is None:
+            ab = _affine_ab(gamma, beta, mean_rstd)
         out = C.conv2d_fwd(xb, wb, stride, ab)
         ctx.save_for_backward(xb, wb, gamma, beta, mean_rstd, ab)
         ctx.stride = stride
@@ -262,14 +277,14 @@ class _ConvBN2dFn(torch.autograd.Function):
             if ctx.needs_input_grad[4] else None
         dx, dgamma, dbeta = C.bn3d_bwd(dz, xb, mean_rstd, gamma, beta, True)
         return (dx.to(ctx.in_dtype), dgamma.to(gamma.dtype),
-                dbeta.to(beta.dtype), None, gw, None)
+                dbeta.to(beta.dtype), None, gw, None, None)
 
 
 def conv_bn2d(x_raw, bn, conv):
     """Fused BN(+ReLU) -> 3x3 Conv2d (the 2D twin of conv_bn3d)."""
-    return _ConvBN2dFn.apply(x_raw, bn.weight, bn.bias,
-                             _bn_mean_rstd(x_raw, bn),
-                             conv.weight, int(conv.stride[0]))
+    mean_rstd, ab = _bn_mean_rstd(x_raw, bn)
+    return _ConvBN2dFn.apply(x_raw, bn.weight, bn.bias, mean_rstd,
+                             conv.weight, int(conv.stride[0]), ab)
 
 
 def _is_3x3_family(conv):

@@ -107,6 +107,10 @@ std::vector<torch::Tensor> bn3d_bwd_res(torch::Tensor dy, torch::Tensor x,
                                         torch::Tensor mean_rstd,
                                         torch::Tensor gamma,
                                         torch::Tensor beta);
+std::vector<torch::Tensor> bn_finalize(
+    torch::Tensor stats, int64_t per_ch, double eps, torch::Tensor gamma,
+    torch::Tensor beta, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double factor);
 torch::Tensor bn3d_infer(torch::Tensor x, torch::Tensor gamma,
                          torch::Tensor beta, torch::Tensor running_mean,
                          torch::Tensor running_var, double eps, bool relu);
@@ -169,6 +173,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn3d_normalize", &bn3d_normalize);
   m.def("bn3d_fwd_res", &bn3d_fwd_res);
   m.def("bn3d_bwd_res", &bn3d_bwd_res);
+  m.def("bn_finalize", &bn_finalize, py::arg("stats"), py::arg("per_ch"),
+        py::arg("eps"), py::arg("gamma"), py::arg("beta"),
+        py::arg("running_mean") = py::none(),
+        py::arg("running_var") = py::none(), py::arg("factor") = 0.0,
+        "one-launch BN finalize of the conv-epilogue partials");
   m.def("bn3d_infer", &bn3d_infer);
   m.def("bn3d_bwd", &bn3d_bwd);
 }

@@ -342,6 +342,106 @@ std::vector<torch::Tensor> bn3d_stats(torch::Tensor x, double eps) {
   return {mean, var, mean_rstd};
 }
 
+// ---- one-launch finalize of the conv-epilogue partials --------------------
+// The per-channel arithmetic between a stats-emitting conv and its consumer
+// (fold the 64 hash slices, mean/var/rstd, the normalize-on-load affine
+// (a, b), the running-stat update) as ONE kernel instead of ~17 torch
+// launches on [C]-sized tensors. One wave per channel: lane l sums slices
+// l, l + 64, ... and the 64 lane sums fold in a shuffle tree, a fixed
+// pairwise order (a sequential sum of the 64 slices loses about two more
+// bits of E[x^2] than torch's sum(0) does, and var = E[x^2] - mean^2
+// cancels). Lane 0 finishes the channel with the same fp32 formulas as
+// the composed chain, every product rounded before it is added (no FMA
+// contraction):
+//   mean = s0/n, var = max(s1/n - mean*mean, 0), rstd = rsqrt(var + eps),
+//   a = gamma*rstd, b = beta - mean*a,
+//   running <- running*(1 - f) + f*batch (running_var: var * n/(n-1)).
+__global__ __launch_bounds__(256) void bn_finalize_kernel(
+    const float* __restrict__ stats,  // [S][C][2]
+    int S, int C, float per_ch, float eps, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ mean,
+    float* __restrict__ var, float* __restrict__ mean_rstd,
+    float* __restrict__ ab, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float keep, float factor,
+    float unbias) {
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int c = blockIdx.x * (blockDim.x / WAVE_SIZE) + threadIdx.x / WAVE_SIZE;
+  if (c >= C) return;  // wave-uniform
+  float s0 = 0.f, s1 = 0.f;
+  for (int s = lane; s < S; s += WAVE_SIZE) {
+    const float* p = stats + ((int64_t)s * C + c) * 2;
+    s0 += p[0];
+    s1 += p[1];
+  }
+  for (int off = WAVE_SIZE / 2; off > 0; off >>= 1) {
+    s0 += __shfl_down(s0, off);
+    s1 += __shfl_down(s1, off);
+  }
+  if (lane != 0) return;
+  const float m = s0 / per_ch;
+  const float v = fmaxf(__fsub_rn(s1 / per_ch, __fmul_rn(m, m)), 0.f);
+  const float rstd = rsqrtf(v + eps);
+  const float a = __fmul_rn(gamma[c], rstd);
+  const float b = __fsub_rn(beta[c], __fmul_rn(m, a));
+  mean[c] = m;
+  var[c] = v;
+  mean_rstd[c * 2] = m;
+  mean_rstd[c * 2 + 1] = rstd;
+  ab[c * 2] = a;
+  ab[c * 2 + 1] = b;
+  if (running_mean != nullptr) {
+    running_mean[c] = __fadd_rn(__fmul_rn(running_mean[c], keep),
+                                __fmul_rn(factor, m));
+    running_var[c] = __fadd_rn(__fmul_rn(running_var[c], keep),
+                               __fmul_rn(factor, __fmul_rn(v, unbias)));
+  }
+}
+
+// returns {mean[C], var[C] (biased), mean_rstd[C][2], ab[C][2]}; with
+// running buffers (fp32, contiguous) also updates them in place
+std::vector<torch::Tensor> bn_finalize(
+    torch::Tensor stats, int64_t per_ch, double eps, torch::Tensor gamma,
+    torch::Tensor beta, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double factor) {
+  CHECK_GPU(stats);
+  TORCH_CHECK(stats.dim() == 3 && stats.size(2) == 2 &&
+              stats.scalar_type() == torch::kFloat32,
+              "stats must be fp32 [S][C][2]");
+  auto st = stats.contiguous();
+  const int S = (int)st.size(0), C = (int)st.size(1);
+  TORCH_CHECK(per_ch > 0, "empty channel");
+  auto g = gamma.detach().to(torch::kFloat32).contiguous();
+  auto b = beta.detach().to(torch::kFloat32).contiguous();
+  TORCH_CHECK(g.is_cuda() && b.is_cuda() && g.numel() == C && b.numel() == C,
+              "gamma/beta must be GPU tensors of C elements");
+  float *rm = nullptr, *rv = nullptr;
+  if (running_mean.has_value() && running_mean->defined()) {
+    TORCH_CHECK(running_var.has_value() && running_var->defined(),
+                "running_mean without running_var");
+    for (const auto* t : {&*running_mean, &*running_var})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                  t->is_contiguous() && t->numel() == C,
+                  "running buffers must be contiguous fp32 GPU [C]");
+    rm = running_mean->data_ptr<float>();
+    rv = running_var->data_ptr<float>();
+  }
+  // one allocation: mean | var | mean_rstd | ab
+  auto buf = torch::empty({6 * (int64_t)C}, st.options());
+  auto mean = buf.narrow(0, 0, C);
+  auto var = buf.narrow(0, C, C);
+  auto mean_rstd = buf.narrow(0, 2 * C, 2 * C).view({C, 2});
+  auto ab = buf.narrow(0, 4 * C, 2 * C).view({C, 2});
+  const double unbias =
+      (double)per_ch / (double)std::max<int64_t>(per_ch - 1, 1);
+  float* o = buf.data_ptr<float>();
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0,
+                     current_stream(), st.data_ptr<float>(), S, C,
+                     (float)per_ch, (float)eps, g.data_ptr<float>(),
+                     b.data_ptr<float>(), o, o + C, o + 2 * C, o + 4 * C, rm,
+                     rv, (float)(1.0 - factor), (float)factor, (float)unbias);
+  return {mean, var, mean_rstd, ab};
+}
+
 torch::Tensor bn3d_infer(torch::Tensor x, torch::Tensor gamma,
                          torch::Tensor beta, torch::Tensor running_mean,
                          torch::Tensor running_var, double eps, bool relu) {

@@ -17,6 +17,7 @@
 //   B[k = (l>>4)*8 + j][col = l&15]
 //   C/D col = l&15, row = (l>>4)*4 + r.
 #include "common.h"
+#include "conv3d_dispatch.h"
 
 #include <hip/hip_bf16.h>
 
@@ -1407,6 +1408,10 @@ torch::Tensor conv3d_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
 torch::Tensor conv3d_dgrad(torch::Tensor go, torch::Tensor w,
                            std::vector<int64_t> in_shape, int64_t stride) {
   CHECK_GPU(go);
+  if (stride == 2 && in_shape.size() == 5 &&
+      s2_dgrad_takes_onepass((int)w.size(0), (int)in_shape[3],
+                             (int)in_shape[4]))
+    return conv3d_dgrad_s2_spatial(go, w, in_shape);
   auto g = go.to(torch::kBFloat16).contiguous();
   auto wc = w.to(torch::kBFloat16).contiguous();
   auto dx = torch::empty(in_shape, g.options());

@@ -21,6 +21,7 @@
 // The stride-2 dgrad (conv3d_dgrad_s2_sp_kernel, below) is its own kernel:
 // 8 parity classes of a dx brick from one staged go slab.
 #include "common.h"
+#include "conv3d_dispatch.h"
 
 #include <hip/hip_bf16.h>
 
@@ -821,7 +822,13 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
   const SpatialPlan plan = plan_spatial(sd, 1, SP_DGRAD);
   auto wb = prep_wb(wc, sd.NCOL, sd.KCH, plan, true);
   sd.Kpad = (int)wb.size(1);
-  auto dx = torch::empty(in_shape, g.options());
+  // On the under-covered grid (plan_spatial, docs/NEXT.md) the kernel never
+  // writes the dx columns past 32 of each gcolt. Until that is fixed they
+  // are at least zero, not whatever the allocator hands back: a training
+  // run must not depend on which tensors were freed before it.
+  const bool undercovered = plan.ncolt < plan.gcolt && sd.NCOL > plan.ncolt;
+  auto dx = undercovered ? torch::zeros(in_shape, g.options())
+                         : torch::empty(in_shape, g.options());
   launch_spatial(g, wb, dx, sd, 1, SP_DGRAD, plan);
   return dx;
 }
@@ -833,9 +840,10 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
 //   p = 0: tap k = 1 at go index i'
 //   p = 1: tap k = 0 at go index i' + 1, and tap k = 2 at go index i'
 // so the 27 taps read the go window at only 8 shifts (dod,doh,dow) in
-// {0,1}^3. A block owns OHT x OWT sub-grid positions at sub-grid depth id'
-// (a 2 x 2*OHT x 2*OWT brick of dx) and stages the channel-innermost slab
-// [2][OHT+1][OWT+1 (row pitch OWT+4)][32 co] once per 32-co tile. K runs
+// {0,1}^3. A block owns OHT x OWT sub-grid positions at DT sub-grid depths
+// from id' (a 2*DT x 2*OHT x 2*OWT brick of dx; OHT = 128 / (OWT*DT)) and
+// stages the channel-innermost slab
+// [DT+1][OHT+1][OWT+1 (row pitch OWT+4)][32 co] once per 32-co tile. K runs
 // (tap, local co): a k-step of 32 is one tap, and lane (row, kg) reads its
 // 8 k as one 16-byte LDS word at lanew[dow] + (shift, fragment) constants.
 // Each shifted fragment is read once and multiplied into every class that
@@ -843,6 +851,13 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
 // 27 x 4 = 108 MFMAs on 8 x 4 accumulator fragments (128 registers).
 // A lane holds the c = 0 and c = 1 accumulators of the same 4 iw', which
 // are 8 consecutive dx elements of one row: one 16-byte store.
+// DT = 2 (OWT 8 only) is the depth-blocked form for 8-wide sub-grid planes:
+// the 128 m are the whole 8 x 8 plane at TWO sub-grid depths id', id' + 1,
+// wave row wm owning depth plane wm. The slab is [3][9][pitch 12][32 co],
+// shift dod of plane p reads slab plane p + dod, and the fragment offsets
+// inside a plane are those of <8>. With an odd sub-grid depth the last
+// block's second plane is past the end: its go planes stage as zeros
+// (od >= D) and its stores are cut by id >= TD.
 // ---------------------------------------------------------------------------
 // class = parity bits (a, b, c) of (id, ih, iw), shift = (dod, doh, dow),
 // both packed depth-major into 3 bits
@@ -877,11 +892,13 @@ constexpr S2TapTable s2_tap_table() {
   return t;
 }
 
-template <int OWT>
+template <int OWT, int DT = 1>
 __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
     const __bf16* __restrict__ go, const __bf16* __restrict__ wb,
     __bf16* __restrict__ dx, SpDims sd) {
-  constexpr int OHT = 128 / OWT;
+  static_assert(DT == 1 || DT == 2, "a wave row owns one depth plane");
+  constexpr int OHT = 128 / (OWT * DT);
+  constexpr int PM = OHT * OWT;  // m per sub-grid depth plane
   constexpr int W2 = OWT + 4;  // OWT+1 used; a row pitch of 4k positions
                                // keeps the OWT-8 two-row fragments off
                                // each other's banks
@@ -893,7 +910,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
   constexpr int NCF = 1;           // column fragments per wave
   constexpr int WCOL = 2 / NCF;    // waves side by side over the columns
   constexpr int MPW = 2 * WCOL;    // m-fragments per wave
-  __shared__ __attribute__((aligned(16))) __bf16 sG[2 * H2 * W2 * 32];
+  static_assert(PM % (MPW * 16) == 0, "a wave's m stay inside one plane");
+  __shared__ __attribute__((aligned(16))) __bf16 sG[(DT + 1) * H2 * W2 * 32];
 
   // the CTILE 32 layout of conv3d_spatial_kernel: 64 B per position, 16-byte
   // chunk ^= 2*bit2(w). Rows of a fragment are dense in w (or whole rows
@@ -923,8 +941,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
   t /= wtiles;
   const int ht = (int)(t % htiles);
   t /= htiles;
-  const int tdp = (int)(t % Dq);     // id' (sub-grid d)
-  const int n = (int)(t / Dq);
+  const int dtiles = (Dq + DT - 1) / DT;
+  const int tdp = (int)(t % dtiles) * DT;  // id' (sub-grid d) of plane 0
+  const int n = (int)(t / dtiles);
   const int oh0 = ht * OHT, ow0 = wt * OWT;
 
   f32x4 acc[8][MPW][NCF];
@@ -942,7 +961,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
   int lanew[2];
 #pragma unroll
   for (int dow = 0; dow < 2; ++dow)
-    lanew[dow] = slab_off(0, m_l / OWT, m_l % OWT + dow, kg * 8);
+    lanew[dow] = slab_off(DT == 1 ? 0 : m_l / PM,
+                          (DT == 1 ? m_l : m_l % PM) / OWT,
+                          m_l % OWT + dow, kg * 8);
   auto frag_off = [](int i) -> int {
     return (((i * 16) / OWT) * W2 + (i * 16) % OWT) * 32;
   };
@@ -960,7 +981,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
   // a thread carries one 8-column vector of 4 adjacent co and stores 8
   // interleaved 8-byte words, as the stride-1 staging does
   constexpr int CG = 4, NCG = 32 / CG;
-  constexpr int NITEM = 2 * H2 * NV * NCG;
+  constexpr int NITEM = (DT + 1) * H2 * NV * NCG;
   const bool wvec = (sd.W & 7) == 0;  // rows 16-byte aligned
 
   for (int kt = 0; kt < kts; ++kt) {
@@ -1004,7 +1025,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
       }
     }
     // the +1 column: one element per (plane, row, co)
-    for (int it = tid; it < 2 * H2 * 32; it += 256) {
+    for (int it = tid; it < (DT + 1) * H2 * 32; it += 256) {
       const int cl = it % 32;
       const int hrow = (it / 32) % H2;
       const int p = it / (32 * H2);
@@ -1059,7 +1080,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
   const int crow0 = (lane >> 4) * 4;
 #pragma unroll
   for (int ab = 0; ab < 4; ++ab) {
-    const int id = 2 * tdp + (ab >> 1);
+    // a wave's m all lie in depth plane wm * MPW * 16 / PM of the block
+    const int id =
+        2 * (tdp + (DT == 1 ? 0 : (wm * MPW * 16) / PM)) + (ab >> 1);
     if (id >= sd.TD) continue;
 #pragma unroll
     for (int i = 0; i < MPW; ++i) {
@@ -1067,7 +1090,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_dgrad_s2_sp_kernel(
       for (int j = 0; j < NCF; ++j) {
         const int col = ncol0 + (wj * NCF + j) * 16 + ccol;
         const int m = (wm * MPW + i) * 16 + crow0;
-        const int ih = 2 * (oh0 + m / OWT) + (ab & 1);
+        const int ih = 2 * (oh0 + (DT == 1 ? m : m % PM) / OWT) + (ab & 1);
         const int iw = 2 * (ow0 + m % OWT);
         if (col >= sd.NCOL || ih >= sd.TH || iw >= sd.TW) continue;
         __bf16* drow = dx + dx_n + ((int64_t)col * sd.TD + id) * THW +
@@ -1144,10 +1167,13 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
   const int Wq = (sd.TW + 1) >> 1, Hq = (sd.TH + 1) >> 1;
   const int Dq = (sd.TD + 1) >> 1;
   const int OWT = Wq % 32 == 0 ? 32 : (Wq % 16 == 0 ? 16 : 8);
-  const int OHT = 128 / OWT;
+  // a whole small plane per block, two sub-grid depths deep
+  const int DT = s2_dgrad_depth_blocked(Hq, Wq) ? 2 : 1;
+  const int OHT = 128 / (OWT * DT);
   const int wtiles = (Wq + OWT - 1) / OWT;
   const int htiles = (Hq + OHT - 1) / OHT;
-  const int64_t nchunks = (int64_t)sd.N * Dq * htiles * wtiles;
+  const int64_t nchunks =
+      (int64_t)sd.N * ((Dq + DT - 1) / DT) * htiles * wtiles;
   TORCH_CHECK(nchunks < (int64_t)1 << 31, "grid too large");
   dim3 grid((unsigned)nchunks, (Cin + 31) / 32);
   auto L = [&](auto kern) {
@@ -1156,7 +1182,8 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
                        reinterpret_cast<const __bf16*>(wb.data_ptr()),
                        reinterpret_cast<__bf16*>(dx.data_ptr()), sd);
   };
-  if (OWT == 32) L(conv3d_dgrad_s2_sp_kernel<32>);
+  if (DT == 2) L(conv3d_dgrad_s2_sp_kernel<8, 2>);
+  else if (OWT == 32) L(conv3d_dgrad_s2_sp_kernel<32>);
   else if (OWT == 16) L(conv3d_dgrad_s2_sp_kernel<16>);
   else L(conv3d_dgrad_s2_sp_kernel<8>);
   return dx;
