@@ -14,13 +14,18 @@ import os
 import torch.nn as nn
 
 from ..ops.bnorm import OpsBatchNorm3d
-from ..ops.conv import OpsConv3d, can_fuse_bn_conv, conv_bn3d
+from ..ops.conv import (OpsConv3d, can_fuse_bn_conv, can_fuse_stem,
+                        conv_bn3d, stem_conv_bn3d)
 
 # Cross-block BN fusion (normalize-on-load): block i's BN+ReLU is applied
 # inside block i+1's conv kernels during slab staging, so the normalized
 # activation never round-trips HBM. COINN_FUSE_BN=0 restores the separate
 # fused-BN-pass path.
 _FUSE_BN = os.environ.get('COINN_FUSE_BN', '1') == '1'
+# Stem pair (conv_0 -> bn_0 -> conv_1) as one autograd node: conv_0's
+# epilogue emits bn_0's statistics and its backward is one pass over the
+# first layer's output. COINN_FUSE_STEM=0 restores the plain fused chain.
+_FUSE_STEM = os.environ.get('COINN_FUSE_STEM', '1') == '1'
 
 
 class _ConvBlock(nn.Module):
@@ -55,8 +60,15 @@ class VBMNet(nn.Module):
                         for i in range(len(blocks) - 1))):
             # fused chain: conv_0 -> [bn_i folded into conv_{i+1}'s load]
             # -> final bn materialized once before the pool
-            x = blocks[0].conv(x)
-            for prev, blk in zip(blocks[:-1], blocks[1:]):
+            first = 1
+            if _FUSE_STEM and can_fuse_stem(blocks[0].conv, blocks[0].bn,
+                                            blocks[1].conv, x):
+                x = stem_conv_bn3d(x, blocks[0].conv, blocks[0].bn,
+                                   blocks[1].conv)
+                first = 2
+            else:
+                x = blocks[0].conv(x)
+            for prev, blk in zip(blocks[first - 1:-1], blocks[first:]):
                 x = conv_bn3d(x, prev.bn, blk.conv)
             x = blocks[-1].bn(x)
         else:

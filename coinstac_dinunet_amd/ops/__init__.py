@@ -4,8 +4,9 @@ Kernel inventory (MI355X equivalents of the ops the reference implicitly
 runs through stock PyTorch — SURVEY.md §2.9):
   - Conv3d fwd/dgrad/wgrad (K1): MFMA spatial-slab tap-reuse kernels
     (stride-1 + stride-2 incl. parity-decomposed dgrad, fused-BN
-    normalize-on-load instances, Cin=1 wgrad specialization) with
-    implicit-GEMM fallbacks — conv3d_spatial.hip / conv3d.hip
+    normalize-on-load instances, Cin=1 wgrad specialization, one-pass
+    BN-backward + wgrad of the Cin=1 first layer) with implicit-GEMM
+    fallbacks — conv3d_spatial.hip / conv3d.hip
   - Conv2d fwd/dgrad/wgrad (ResNet): igemm (3x3 + 7x7 stem), spatial
     slab, tap-reuse + split-K wgrad, parity s2 dgrad — conv2d.hip
   - pointwise 1x1 convs as batched MFMA GEMMs     — pointwise.hip

@@ -8,6 +8,9 @@ GPU paths (bf16):
   - conv_bn3d / conv_bn2d: the PREVIOUS block's BN(+ReLU) folded into the
     conv's input staging (normalize-on-load), with the conv epilogue
     emitting the next BN's statistics.
+  - stem_conv_bn3d: the Cin = 1 first conv, its BN and the second conv as
+    one node — statistics from the first conv's epilogue, BN-backward and
+    the first conv's wgrad as one pass over its output.
 CPU falls back to torch.nn.functional convs.
 """
 import os
@@ -122,6 +125,24 @@ class _Conv3dFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
+def _fused_fwd3d(C, xb, wb, bias, stride, ab):
+    """Normalize-on-load forward of a 3x3x3 conv: (out, stats or None)."""
+    stats = None
+    if route_fused_fwd3d(xb.size(1), xb.size(3), xb.size(4),
+                         stride) == 'spatial':
+        if bias is None:
+            # epilogue also emits this output's BN statistics — the
+            # next fused pair skips its bn_reduce pass entirely
+            out, stats = C.conv3d_fwd_spatial_stats(xb, wb, stride, ab)
+        else:
+            out = C.conv3d_fwd_spatial(xb, wb, stride, 0, ab)
+    else:
+        out = C.conv3d_fwd(xb, wb, stride, ab)
+    if bias is not None:
+        out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
+    return out, stats
+
+
 class _ConvBNFn(torch.autograd.Function):
     """Previous block's BN(+ReLU) folded into this conv's input load.
 
@@ -144,19 +165,7 @@ class _ConvBNFn(torch.autograd.Function):
         wb = weight.to(torch.bfloat16)
         if ab is None:
             ab = _affine_ab(gamma, beta, mean_rstd)
-        stats = None
-        if route_fused_fwd3d(xb.size(1), xb.size(3), xb.size(4),
-                             stride) == 'spatial':
-            if bias is None:
-                # epilogue also emits this output's BN statistics — the
-                # next fused pair skips its bn_reduce pass entirely
-                out, stats = C.conv3d_fwd_spatial_stats(xb, wb, stride, ab)
-            else:
-                out = C.conv3d_fwd_spatial(xb, wb, stride, 0, ab)
-        else:
-            out = C.conv3d_fwd(xb, wb, stride, ab)
-        if bias is not None:
-            out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
+        out, stats = _fused_fwd3d(C, xb, wb, bias, stride, ab)
         ctx.save_for_backward(xb, wb, gamma, beta, mean_rstd, ab)
         ctx.stride = stride
         ctx.has_bias = bias is not None
@@ -197,6 +206,83 @@ def conv_bn3d(x_raw, bn, conv):
     out, stats = _ConvBNFn.apply(x_raw, bn.weight, bn.bias, mean_rstd,
                                  conv.weight, conv.bias,
                                  int(conv.stride[0]), ab)
+    if stats.numel() > 0:
+        out._coinn_bn_stats = stats
+    return out
+
+
+class _StemConvBNFn(torch.autograd.Function):
+    """conv0 (Cin = 1) -> bn0(+ReLU) folded into conv1, as one node.
+
+    Forward: conv0 on the single-channel instances whose epilogue emits
+    bn0's statistics, the one-launch finalize, then conv1's normalize-on-
+    load forward. Backward: conv0's input is the image, so the gradient of
+    its raw output has one consumer, conv0's wgrad; BN-backward and that
+    wgrad are linear in per-channel sums over positions and run as ONE pass
+    over (x, dz, x1) — the BN input gradient never exists.
+    """
+
+    @staticmethod
+    def forward(ctx, x, w0, gamma, beta, w1, bias1, stride1, bn0):
+        C = require_native()
+        xb = x.to(torch.bfloat16)
+        w0b = w0.to(torch.bfloat16)
+        w1b = w1.to(torch.bfloat16)
+        x1, stats0 = C.conv3d_fwd_ci1_stats(xb, w0b)
+        x1._coinn_bn_stats = stats0
+        _, _, mean_rstd, ab = bn_finalize_attached(x1, bn0,
+                                                   bn_momentum_step(bn0))
+        out, stats = _fused_fwd3d(C, x1, w1b, bias1, stride1, ab)
+        ctx.save_for_backward(xb, x1, w1b, gamma, beta, mean_rstd, ab)
+        ctx.stride1 = stride1
+        ctx.has_bias1 = bias1 is not None
+        ctx.w0_dtype = w0.dtype
+        ctx.w1_dtype = w1.dtype
+        if stats is None:
+            stats = torch.empty(0, device=out.device)
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_stats):
+        C = require_native()
+        xb, x1, w1b, gamma, beta, mean_rstd, ab = ctx.saved_tensors
+        go = grad_out.to(torch.bfloat16).contiguous()
+        stride1 = ctx.stride1
+        dz = _dgrad3d(C, go, w1b, list(x1.shape), stride1)
+        gw1 = C.conv3d_wgrad(x1, go, stride1, 0, ab).to(ctx.w1_dtype) \
+            if ctx.needs_input_grad[4] else None
+        gb1 = C.channel_sum(go) if (ctx.has_bias1
+                                    and ctx.needs_input_grad[5]) else None
+        gw0 = dgamma = dbeta = None
+        if any(ctx.needs_input_grad[1:4]):
+            gw0, dgamma, dbeta = C.conv3d_wgrad_ci1_bn(
+                xb, dz, x1, mean_rstd, gamma, beta)
+            gw0 = gw0.to(ctx.w0_dtype)
+            dgamma, dbeta = dgamma.to(gamma.dtype), dbeta.to(beta.dtype)
+        return None, gw0, dgamma, dbeta, gw1, gb1, None, None
+
+
+def can_fuse_stem(conv0, bn0, conv1, x):
+    """True when (conv0 -> bn0 -> conv1) runs as _StemConvBNFn: conv0 is a
+    bias-free stride-1 Cin = 1 conv on the image (no input gradient), bn0
+    uses batch statistics, and the shape fits the one-pass backward."""
+    if not (conv0.in_channels == 1 and conv0.bias is None
+            and conv0.stride == (1, 1, 1) and _is_3x3_family(conv0)
+            and not x.requires_grad and bn0.training
+            and can_fuse_bn_conv(bn0, conv1, x) and x.dim() == 5):
+        return False
+    H, W = x.size(3), x.size(4)
+    return (route_fwd3d(1, H, W, 1) == 'spatial-ctile1'
+            and require_native().conv3d_wgrad_ci1_bn_fits(H, W))
+
+
+def stem_conv_bn3d(x, conv0, bn0, conv1):
+    """conv1(relu(bn0(conv0(x)))) for a stem that can_fuse_stem accepts;
+    running statistics update exactly as in the unfused modules."""
+    out, stats = _StemConvBNFn.apply(x, conv0.weight, bn0.weight, bn0.bias,
+                                     conv1.weight, conv1.bias,
+                                     int(conv1.stride[0]), bn0)
     if stats.numel() > 0:
         out._coinn_bn_stats = stats
     return out

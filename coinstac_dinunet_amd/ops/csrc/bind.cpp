@@ -63,6 +63,10 @@ torch::Tensor conv3d_dgrad(torch::Tensor go, torch::Tensor w,
 torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go, int64_t stride,
                            int64_t variant, c10::optional<torch::Tensor> bn_ab);
 torch::Tensor channel_sum(torch::Tensor go);
+bool conv3d_wgrad_ci1_bn_fits(int64_t H, int64_t W);
+std::vector<torch::Tensor> conv3d_wgrad_ci1_bn(
+    torch::Tensor x_in, torch::Tensor dz, torch::Tensor x1,
+    torch::Tensor mean_rstd, torch::Tensor gamma, torch::Tensor beta);
 // conv3d_spatial.hip
 torch::Tensor conv3d_fwd_spatial(torch::Tensor x, torch::Tensor w,
                                  int64_t stride, int64_t ctile_opt,
@@ -70,6 +74,8 @@ torch::Tensor conv3d_fwd_spatial(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> conv3d_fwd_spatial_stats(
     torch::Tensor x, torch::Tensor w, int64_t stride,
     c10::optional<torch::Tensor> bn_ab);
+std::vector<torch::Tensor> conv3d_fwd_ci1_stats(torch::Tensor x,
+                                                torch::Tensor w);
 torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
                                    std::vector<int64_t> in_shape);
 torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
@@ -149,12 +155,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("variant") = 0,
         py::arg("bn_ab") = py::none());
   m.def("channel_sum", &channel_sum);
+  m.def("conv3d_wgrad_ci1_bn_fits", &conv3d_wgrad_ci1_bn_fits);
+  m.def("conv3d_wgrad_ci1_bn", &conv3d_wgrad_ci1_bn,
+        "one-pass BN-backward + wgrad of a Cin = 1 conv");
   m.def("conv3d_fwd_spatial", &conv3d_fwd_spatial,
         py::arg("x"), py::arg("w"), py::arg("stride"),
         py::arg("ctile_opt") = 0, py::arg("bn_ab") = py::none());
   m.def("conv3d_fwd_spatial_stats", &conv3d_fwd_spatial_stats,
         py::arg("x"), py::arg("w"), py::arg("stride"),
         py::arg("bn_ab") = py::none());
+  m.def("conv3d_fwd_ci1_stats", &conv3d_fwd_ci1_stats,
+        "CTILE-1 forward + epilogue BN statistics");
   m.def("conv3d_dgrad_spatial", &conv3d_dgrad_spatial);
   m.def("conv3d_dgrad_s2_spatial", &conv3d_dgrad_s2_spatial);
   m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"),

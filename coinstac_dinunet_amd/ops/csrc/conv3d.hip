@@ -576,6 +576,352 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_ci1_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// BN-backward + WGRAD of a Cin=1 layer in ONE pass over (x, dz, x1).
+// x1 is the layer's raw output, dz the gradient of relu(bn(x1)). With
+// d = dz*[g*xhat + beta > 0], xhat = (x1 - mean)*rstd, the composed path
+// (bn3d_bwd, then conv3d_wgrad_ci1_kernel on its bf16 output) is linear in
+//   A[co][tap] = sum d*x(tap)   P[co][tap] = sum x1*x(tap)
+//   B[tap] = sum x(tap)         s[co] = sum d        q[co] = sum d*x1
+// so the BN input gradient never has to exist. A block owns (n, a group of
+// at most 8 output depth planes, 32 co). The single-channel x slab is a
+// ring of 3 planes [H+2][W+8] in LDS (one new plane staged per output
+// plane); the taps are the MFMA B fragments, read as one aligned 16-byte
+// word plus one dword and shifted into place per lane (kw = 0, 1, 2) with
+// v_alignbit. The two big tensors never touch LDS: with m as the
+// contraction index, lane (co, kg) of an A fragment holds 8 consecutive m of
+// ONE channel row, which is a 16-byte global load; an item is 32*NS
+// consecutive m of a row, so the 4 kg lanes use whole 128-byte lines at
+// NS = 2. dz is masked in registers (the mask expression is
+// bn_bwd_reduce_kernel's), both operands enter the MFMAs as the exact bf16
+// from memory, and s, q accumulate per lane in fp32 on the way. B comes from
+// a ones A fragment. Items are loaded one ahead of the MFMAs, across rows
+// and planes. Each block writes its fp32 partials to its own slice with
+// plain stores; the finish kernel folds the slices and forms
+//   sx = rstd*(q - mean*s), C = rstd*(P - mean*B), dbeta = s, dgamma = sx,
+//   dw = g*rstd*(A - (s/n)*B - (sx/n)*C)
+// in double: deterministic, no atomics.
+// Requires: Cin==1, stride==1, OW % 32 == 0, slab fits.
+// ---------------------------------------------------------------------------
+// partial slice (floats): A[32][32] | P[32][32] | B[32] | s[32] | q[32]
+#define CI1BN_PS 2144
+#define CI1BN_TARGET_BLOCKS 1024
+
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+static inline size_t ci1bn_lds_bytes(int64_t H, int64_t W) {
+  return (size_t)(3 * (H + 2) * (W + 8)) * sizeof(__bf16) +
+         4 * 256 * sizeof(float);
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void conv3d_wgrad_ci1_bn_kernel(
+    const __bf16* __restrict__ x, const __bf16* __restrict__ dz,
+    const __bf16* __restrict__ x1, const float* __restrict__ mean_rstd,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ part, ConvDims cd, int od_groups) {
+  const int WP = cd.W + 8;  // p = iw + 1; columns W+2.. pad rows to 16 B
+  const int H2 = cd.H + 2;
+  extern __shared__ __attribute__((aligned(16))) __bf16 smem_ci1bn[];
+  __bf16* sX = smem_ci1bn;                                   // [3][H2][WP]
+  float* red = reinterpret_cast<float*>(sX + 3 * H2 * WP);   // [4][256]
+
+  const int n = blockIdx.x;
+  const int og = blockIdx.y;
+  const int co0 = blockIdx.z * 32;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int row = lane & 15, kg = lane >> 4;
+
+  const int64_t HW = (int64_t)cd.H * cd.W;
+  const int64_t OHW = (int64_t)cd.OH * cd.OW;
+  const int od_per = (cd.OD + od_groups - 1) / od_groups;
+  const int od_lo = og * od_per;
+  const int od_hi = min(cd.OD, od_lo + od_per);
+  const int nms = cd.OW / (32 * NS);
+  const int nitems = cd.OH * nms;
+
+  // lane constants: BN of co = co0 + i*16 + row (A side), tap t*16 + row
+  // (B side; taps 27..31 re-read tap 26, their columns are never used)
+  float mean[2], rstd[2], gm[2], bt[2];
+  bool cok[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int co = co0 + i * 16 + row;
+    cok[i] = co < cd.Cout;
+    mean[i] = cok[i] ? mean_rstd[co * 2] : 0.f;
+    rstd[i] = cok[i] ? mean_rstd[co * 2 + 1] : 0.f;
+    gm[i] = cok[i] ? gamma[co] : 0.f;
+    bt[i] = cok[i] ? beta[co] : -1.f;
+  }
+  int kdv[2], tapoff[2];
+  unsigned shift[2];
+  bool kw2[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int tap = min(t * 16 + row, 26);
+    const int kd = tap / 9, r9 = tap - kd * 9;
+    const int kh = r9 / 3, kw = r9 % 3;
+    kdv[t] = kd;
+    tapoff[t] = kh * WP;
+    shift[t] = kw == 1 ? 16u : 0u;
+    kw2[t] = kw == 2;
+  }
+
+  // plane id of x into ring slot (id + 3) % 3; id = -1 and id = D are zero
+  auto stage_plane = [&](int id) {
+    __bf16* dst = sX + ((id + 3) % 3) * H2 * WP;
+    const bool pok = (unsigned)id < (unsigned)cd.D;
+    const int nv = cd.W / 8 + 1;
+    for (int it = tid; it < H2 * nv; it += 256) {
+      const int ihp = it / nv, v = it - ihp * nv;
+      __bf16* drow = dst + ihp * WP;
+      if (v == nv - 1) {  // the two halo columns
+        drow[0] = (__bf16)0.f;
+        drow[cd.W + 1] = (__bf16)0.f;
+        continue;
+      }
+      const int ih = ihp - 1;
+      bf16x8 vec = bf16x8{};
+      if (pok && (unsigned)ih < (unsigned)cd.H)
+        vec = *reinterpret_cast<const bf16x8*>(
+            x + ((int64_t)n * cd.D + id) * HW + (int64_t)ih * cd.W + v * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) drow[1 + v * 8 + j] = vec[j];
+    }
+  };
+
+  // item it of plane od: 32*NS consecutive m of row it / nms
+  auto load_item = [&](int od, int it, bf16x8 (&d)[NS][2],
+                       bf16x8 (&xv)[NS][2]) {
+    const int oh = it / nms;
+    const int owb = (it - oh * nms) * (32 * NS) + kg * 8;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t base =
+          (((int64_t)n * cd.Cout + co0 + i * 16 + row) * cd.OD + od) * OHW +
+          (int64_t)oh * cd.OW + owb;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (cok[i]) {
+          d[s][i] = *reinterpret_cast<const bf16x8*>(dz + base + s * 32);
+          xv[s][i] = *reinterpret_cast<const bf16x8*>(x1 + base + s * 32);
+        } else {
+          d[s][i] = bf16x8{};
+          xv[s][i] = bf16x8{};
+        }
+      }
+    }
+  };
+
+  f32x4 accA[2][2], accP[2][2], accB[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    accB[i] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      accA[i][t] = {0.f, 0.f, 0.f, 0.f};
+      accP[i][t] = {0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  float ssum[2] = {0.f, 0.f}, qsum[2] = {0.f, 0.f};
+  bf16x8 ones;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.f;
+
+  bf16x8 cur_d[NS][2], cur_x[NS][2], nxt_d[NS][2], nxt_x[NS][2];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      cur_d[s][i] = bf16x8{}; cur_x[s][i] = bf16x8{};
+      nxt_d[s][i] = bf16x8{}; nxt_x[s][i] = bf16x8{};
+    }
+  if (od_lo < od_hi && wave < nitems) load_item(od_lo, wave, cur_d, cur_x);
+
+  for (int od = od_lo; od < od_hi; ++od) {
+    // plane od + 1 replaces plane od - 2, which the previous iteration's
+    // taps no longer read once every wave is here
+    __syncthreads();
+    if (od == od_lo) {
+      stage_plane(od - 1);
+      stage_plane(od);
+    }
+    stage_plane(od + 1);
+    __syncthreads();
+    int poff[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+      poff[t] = ((od + 2 + kdv[t]) % 3) * H2 * WP + tapoff[t];
+
+    for (int it = wave; it < nitems; it += 4) {
+      int nit = it + 4, nod = od;
+      if (nit >= nitems) {
+        nit = wave;
+        nod = od + 1;
+      }
+      const bool more = nod < od_hi;
+      if (more) load_item(nod, nit, nxt_d, nxt_x);
+
+      const int oh = it / nms;
+      const int owb = (it - oh * nms) * (32 * NS) + kg * 8;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        // tap fragments: elements kw .. kw + 7 of the 10 at the aligned
+        // position p = ow of slab row oh + kh
+        bf16x8 bfrag[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const __bf16* src = sX + poff[t] + oh * WP + owb + s * 32;
+          const u32x4 q4 = *reinterpret_cast<const u32x4*>(src);
+          const unsigned q5 = *reinterpret_cast<const unsigned*>(src + 8);
+          unsigned lo[5];
+          lo[0] = kw2[t] ? q4[1] : q4[0];
+          lo[1] = kw2[t] ? q4[2] : q4[1];
+          lo[2] = kw2[t] ? q4[3] : q4[2];
+          lo[3] = kw2[t] ? q5 : q4[3];
+          lo[4] = q5;
+          u32x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            o[e] = __builtin_amdgcn_alignbit(lo[e + 1], lo[e], shift[t]);
+          bfrag[t] = __builtin_bit_cast(bf16x8, o);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          bf16x8 dm;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float xf = (float)cur_x[s][i][j];
+            float df = (float)cur_d[s][i][j];
+            const float xh = (xf - mean[i]) * rstd[i];
+            const float z = gm[i] * xh + bt[i];
+            const bool keep = !(z <= 0.f);
+            dm[j] = keep ? cur_d[s][i][j] : (__bf16)0.f;
+            df = keep ? df : 0.f;
+            ssum[i] += df;
+            qsum[i] += df * xf;
+          }
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            accA[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                dm, bfrag[t], accA[i][t], 0, 0, 0);
+            accP[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                cur_x[s][i], bfrag[t], accP[i][t], 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          accB[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              ones, bfrag[t], accB[t], 0, 0, 0);
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          cur_d[s][i] = nxt_d[s][i];
+          cur_x[s][i] = nxt_x[s][i];
+        }
+    }
+  }
+
+  // ---- block partials: the 4 waves fold through LDS in a fixed order ----
+  float* slice = part + ((int64_t)blockIdx.z * gridDim.x * gridDim.y +
+                         (int64_t)n * gridDim.y + og) * CI1BN_PS;
+  // kind 0 = A, 1 = P (co = i*16 + .., tap = t*16 + ..), 2 = B (any row)
+  auto fold = [&](const f32x4& a, int kind, int i, int t) {
+    *reinterpret_cast<f32x4*>(red + wave * 256 + lane * 4) = a;
+    __syncthreads();
+    const float v = red[tid] + red[256 + tid] + red[512 + tid] +
+                    red[768 + tid];
+    const int l = tid >> 2, r = tid & 3;
+    const int co_l = i * 16 + (l >> 4) * 4 + r;
+    const int tap = t * 16 + (l & 15);
+    if (kind < 2) slice[kind * 1024 + co_l * 32 + tap] = v;
+    else if ((l >> 4) == 0 && r == 0) slice[2048 + tap] = v;
+    __syncthreads();
+  };
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      fold(accA[i][t], 0, i, t);
+      fold(accP[i][t], 1, i, t);
+    }
+#pragma unroll
+  for (int t = 0; t < 2; ++t) fold(accB[t], 2, 0, t);
+
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    ssum[i] += __shfl_xor(ssum[i], 16);
+    ssum[i] += __shfl_xor(ssum[i], 32);
+    qsum[i] += __shfl_xor(qsum[i], 16);
+    qsum[i] += __shfl_xor(qsum[i], 32);
+  }
+  if (kg == 0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      red[wave * 64 + (i * 16 + row) * 2] = ssum[i];
+      red[wave * 64 + (i * 16 + row) * 2 + 1] = qsum[i];
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const float v = red[tid] + red[64 + tid] + red[128 + tid] +
+                    red[192 + tid];
+    slice[((tid & 1) ? 2112 : 2080) + (tid >> 1)] = v;
+  }
+}
+
+// One block per output channel: 32 groups of 32 lanes (lane = tap) walk the
+// channel tile's nb slices, everything in double from the first add on.
+__global__ __launch_bounds__(1024) void conv3d_wgrad_ci1_bn_finish_kernel(
+    const float* __restrict__ part, int nb,
+    const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
+    double per_ch, float* __restrict__ dw, float* __restrict__ dgamma,
+    float* __restrict__ dbeta) {
+  const int co = blockIdx.x, col = co & 31;
+  const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  const float* base = part + (int64_t)(co >> 5) * nb * CI1BN_PS;
+  double a = 0., p = 0., b = 0., s = 0., q = 0.;
+#pragma unroll 4
+  for (int k = grp; k < nb; k += 32) {
+    const float* sl = base + (int64_t)k * CI1BN_PS;
+    a += (double)sl[col * 32 + lane];
+    p += (double)sl[1024 + col * 32 + lane];
+    b += (double)sl[2048 + lane];
+    s += (double)sl[2080 + col];
+    q += (double)sl[2112 + col];
+  }
+  __shared__ double sh[5][32][32];
+  sh[0][grp][lane] = a;
+  sh[1][grp][lane] = p;
+  sh[2][grp][lane] = b;
+  sh[3][grp][lane] = s;
+  sh[4][grp][lane] = q;
+  __syncthreads();
+  if (threadIdx.x >= 32) return;
+  a = p = b = s = q = 0.;
+  for (int g = 0; g < 32; ++g) {
+    a += sh[0][g][lane];
+    p += sh[1][g][lane];
+    b += sh[2][g][lane];
+    s += sh[3][g][lane];
+    q += sh[4][g][lane];
+  }
+  const double mean = (double)mean_rstd[co * 2];
+  const double rstd = (double)mean_rstd[co * 2 + 1];
+  const double sx = rstd * (q - mean * s);
+  const double chat = rstd * (p - mean * b);
+  const double v = (double)gamma[co] * rstd *
+                   (a - (s / per_ch) * b - (sx / per_ch) * chat);
+  if (lane < 27) dw[co * 27 + lane] = (float)v;
+  if (lane == 0) {
+    dgamma[co] = (float)sx;
+    dbeta[co] = (float)s;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Stride-2 DGRAD, parity-decomposed: the dense mask formulation wastes 7/8
 // of the MFMA work (only taps with (id+1-kd) even contribute). Decompose
 // dx by (id,ih,iw) mod 2 into 8 classes; each class is a DENSE implicit
@@ -1609,6 +1955,88 @@ torch::Tensor conv3d_wgrad(torch::Tensor x, torch::Tensor go,
   if (fuse) LSK(conv3d_wgrad_kernel<true>);
   else LSK(conv3d_wgrad_kernel<false>);
   return dw.view({cd.Cout, cd.Cin, 3, 3, 3});
+}
+
+// bnorm.hip
+std::vector<torch::Tensor> bn3d_bwd(torch::Tensor dy, torch::Tensor x,
+                                    torch::Tensor mean_rstd,
+                                    torch::Tensor gamma, torch::Tensor beta,
+                                    bool relu);
+
+// shape conditions of the one-pass kernel beyond Cin == 1, stride 1
+bool conv3d_wgrad_ci1_bn_fits(int64_t H, int64_t W) {
+  return H >= 1 && W >= 32 && W % 32 == 0 &&
+         ci1bn_lds_bytes(H, W) <= 64 * 1024;
+}
+
+// BN(+ReLU)-backward of x1 = conv(x_in) fused with that conv's wgrad:
+// {dw[Cout,1,3,3,3], dgamma[Cout], dbeta[Cout]} (fp32) from dz, the
+// gradient of relu(bn(x1)). Shapes the one-pass kernel does not cover run
+// bn3d_bwd followed by conv3d_wgrad.
+std::vector<torch::Tensor> conv3d_wgrad_ci1_bn(
+    torch::Tensor x_in, torch::Tensor dz, torch::Tensor x1,
+    torch::Tensor mean_rstd, torch::Tensor gamma, torch::Tensor beta) {
+  CHECK_GPU(x_in);
+  CHECK_GPU(dz);
+  CHECK_GPU(x1);
+  auto xc = x_in.to(torch::kBFloat16).contiguous();
+  auto dzc = dz.to(torch::kBFloat16).contiguous();
+  auto x1c = x1.to(torch::kBFloat16).contiguous();
+  TORCH_CHECK(xc.dim() == 5 && dzc.dim() == 5 && x1c.sizes() == dzc.sizes() &&
+              xc.size(0) == dzc.size(0), "x_in / dz / x1 shape mismatch");
+  ConvDims cd;
+  cd.N = (int)xc.size(0); cd.Cin = (int)xc.size(1);
+  cd.D = (int)xc.size(2); cd.H = (int)xc.size(3); cd.W = (int)xc.size(4);
+  cd.Cout = (int)dzc.size(1);
+  cd.stride = 1;
+  cd.OD = (int)dzc.size(2); cd.OH = (int)dzc.size(3); cd.OW = (int)dzc.size(4);
+  TORCH_CHECK(cd.OD == cd.D && cd.OH == cd.H && cd.OW == cd.W,
+              "stride-1 3x3x3 pad-1 conv: output plane == input plane");
+  auto mr = mean_rstd.to(torch::kFloat32).contiguous();
+  auto g = gamma.detach().to(torch::kFloat32).contiguous();
+  auto b = beta.detach().to(torch::kFloat32).contiguous();
+  TORCH_CHECK(mr.numel() == 2 * cd.Cout && g.numel() == cd.Cout &&
+              b.numel() == cd.Cout, "mean_rstd [C,2], gamma [C], beta [C]");
+
+  if (cd.Cin != 1 || !conv3d_wgrad_ci1_bn_fits(cd.H, cd.W)) {
+    auto r = bn3d_bwd(dzc, x1c, mr, g, b, true);
+    return {conv3d_wgrad(xc, r[0], 1, 0, c10::nullopt), r[1], r[2]};
+  }
+
+  const int co_t = (cd.Cout + 31) / 32;
+  // a block covers at most 8 depth planes (the fp32 partials stay bounded)
+  int od_groups = std::max((cd.OD + 7) / 8,
+                           CI1BN_TARGET_BLOCKS / std::max(cd.N * co_t, 1));
+  od_groups = std::max(1, std::min(cd.OD, od_groups));
+  // no empty groups: every group starts inside the depth range
+  const int od_per = (cd.OD + od_groups - 1) / od_groups;
+  od_groups = (cd.OD + od_per - 1) / od_per;
+  const int nb = cd.N * od_groups;
+  auto fopt = xc.options().dtype(torch::kFloat32);
+  auto part = torch::empty({(int64_t)co_t, (int64_t)nb, (int64_t)CI1BN_PS},
+                           fopt);
+  auto dw = torch::empty({cd.Cout, 1, 3, 3, 3}, fopt);
+  auto dgamma = torch::empty({cd.Cout}, fopt);
+  auto dbeta = torch::empty({cd.Cout}, fopt);
+  const size_t lds = ci1bn_lds_bytes(cd.H, cd.W);
+  dim3 grid(cd.N, od_groups, co_t);
+  auto s = current_stream();
+  dispatch_bool(cd.OW % 64 == 0, [&](auto wide) {
+    hipLaunchKernelGGL(
+        (conv3d_wgrad_ci1_bn_kernel<decltype(wide)::value ? 2 : 1>), grid,
+        dim3(256), lds, s, reinterpret_cast<const __bf16*>(xc.data_ptr()),
+        reinterpret_cast<const __bf16*>(dzc.data_ptr()),
+        reinterpret_cast<const __bf16*>(x1c.data_ptr()),
+        mr.data_ptr<float>(), g.data_ptr<float>(), b.data_ptr<float>(),
+        part.data_ptr<float>(), cd, od_groups);
+  });
+  const double per_ch = (double)cd.N * cd.OD * cd.OH * cd.OW;
+  hipLaunchKernelGGL(conv3d_wgrad_ci1_bn_finish_kernel, dim3(cd.Cout),
+                     dim3(1024), 0, s, part.data_ptr<float>(), nb,
+                     mr.data_ptr<float>(), g.data_ptr<float>(), per_ch,
+                     dw.data_ptr<float>(), dgamma.data_ptr<float>(),
+                     dbeta.data_ptr<float>());
+  return {dw, dgamma, dbeta};
 }
 
 torch::Tensor channel_sum(torch::Tensor go) {

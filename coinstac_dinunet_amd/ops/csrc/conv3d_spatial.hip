@@ -540,6 +540,7 @@ static SpDims make_spdims(const torch::Tensor& in, int ncol, int td, int th,
 enum SpMode {
   SP_PLAIN,        // forward
   SP_CTILE1,       // forward, Cin < 16 (stride 1): single-channel tiles
+  SP_CTILE1_STATS,  // ... and the epilogue BN statistics
   SP_FUSED,        // forward with normalize-on-load
   SP_FUSED_STATS,  // ... and the epilogue BN statistics
   SP_DGRAD,        // stride-1 input gradient (go in, tap-flipped weights)
@@ -555,7 +556,8 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
   SpatialPlan p;
   p.owt = sd.TW % 32 == 0 ? 32 : (sd.TW % 16 == 0 ? 16 : 8);
   p.chunk = stride == 1 ? 256 : 128;
-  p.ctile = mode == SP_CTILE1 ? 1 : (stride == 1 ? 32 : 16);
+  const bool ctile1 = mode == SP_CTILE1 || mode == SP_CTILE1_STATS;
+  p.ctile = ctile1 ? 1 : (stride == 1 ? 32 : 16);
   p.ncolt = p.gcolt = 32;
   p.dt = 1;
   const bool fused = mode == SP_FUSED || mode == SP_FUSED_STATS;
@@ -584,7 +586,7 @@ static SpatialPlan plan_spatial(const SpDims& sd, int stride, SpMode mode) {
     p.owt = 8;  // the chunk-64 instances are OWT=8
     // swept on MI355X (r2): 128-col instances won at the deep layers
     // (37.7 vs 38.2 ms/step flagship) — slab re-reads drop 4x vs 32-col
-    if (sd.NCOL >= 64 && mode != SP_CTILE1)
+    if (sd.NCOL >= 64 && !ctile1)
       p.gcolt = sd.NCOL >= 128 ? 128 : 64;
     // one tile is the whole output plane (d8-class forwards): depth-blocked
     // instances, one (DT, column tile) per stride whatever NCOL is — 4
@@ -689,15 +691,19 @@ static void launch_spatial(torch::Tensor in, torch::Tensor wb,
   const std::false_type plain{};
   if (p.ctile == 1) {
     // single-channel (first-layer) instances: one 32-k-step covers the
-    // whole 27-tap K, slab is [1][3][H2][W2]; plain epilogue only
-    if (p.chunk == 64)
-      K(IntC<8>{}, IntC<1>{}, IntC<1>{}, IntC<64>{}, plain, IntC<0>{},
-        IntC<32>{}, dt1);
-    else
-      with_owt([&](auto owt) {
-        K(owt, IntC<1>{}, IntC<1>{}, IntC<256>{}, plain, IntC<0>{},
+    // whole 27-tap K, slab is [1][3][H2][W2]; plain staging, with or
+    // without the epilogue statistics
+    dispatch_bool(mode == SP_CTILE1_STATS, [&](auto st) {
+      const IntC<decltype(st)::value ? 1 : 0> sm{};
+      if (p.chunk == 64)
+        K(IntC<8>{}, IntC<1>{}, IntC<1>{}, IntC<64>{}, plain, sm,
           IntC<32>{}, dt1);
-      });
+      else
+        with_owt([&](auto owt) {
+          K(owt, IntC<1>{}, IntC<1>{}, IntC<256>{}, plain, sm, IntC<32>{},
+            dt1);
+        });
+    });
   } else if (p.chunk == 512) {
     // plain (dgrad) and fused+stats (fwd) only
     dispatch_bool(mode == SP_FUSED_STATS, [&](auto fs) {
@@ -776,7 +782,7 @@ static std::vector<torch::Tensor> spatial_fwd(torch::Tensor x,
   auto out = torch::empty({sd.N, sd.NCOL, sd.TD, sd.TH, sd.TW},
                           xc.options());
   // stats[64][Cout][2]: hash-sliced partial sums; callers fold with sum(0)
-  if (mode == SP_FUSED_STATS)
+  if (mode == SP_FUSED_STATS || mode == SP_CTILE1_STATS)
     stats = torch::zeros({64, sd.NCOL, 2},
                          xc.options().dtype(torch::kFloat32));
   launch_spatial(xc, wb, out, sd, stride, mode, plan,
@@ -808,6 +814,13 @@ std::vector<torch::Tensor> conv3d_fwd_spatial_stats(
   TORCH_CHECK(bn_ab.defined() && bn_ab.numel() > 0,
               "stats form requires the fused-BN path");
   return spatial_fwd(x, w, (int)stride, SP_FUSED_STATS, bn_ab);
+}
+
+// single-channel-tile stride-1 forward (the first layer) + epilogue BN
+// statistics: out is bitwise conv3d_fwd_spatial(x, w, 1, 1)
+std::vector<torch::Tensor> conv3d_fwd_ci1_stats(torch::Tensor x,
+                                                torch::Tensor w) {
+  return spatial_fwd(x, w, 1, SP_CTILE1_STATS, torch::Tensor());
 }
 
 torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
