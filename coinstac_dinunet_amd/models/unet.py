@@ -8,9 +8,13 @@ MI355X mapping: every conv is a 3x3x3/pad-1 stride-1 or stride-2
 OpsConv3d, so the whole encoder/decoder runs on the spatial-slab MFMA
 kernels; BN+ReLU are the fused bnorm kernels. Downsampling is stride-2
 convolution (not pooling) and upsampling is nearest-neighbor interp +
-conv — both stay inside the supported kernel family, no transposed-conv
-kernel needed. Skip connections go through safe_concat (center-crop) so
-odd input sizes work.
+conv, no transposed-conv kernel needed. Where the skip is exactly twice the
+decoder input (even sizes) the pair runs as ops.upsample2_conv3d: 8 parity
+classes of 2x2x2 convs on the low-res input (upconv3d.hip), so the 8x
+upsampled activation is never written, read or kept for backward.
+COINN_FUSE_UPSAMPLE=0 restores interpolate + conv, which odd skip sizes
+always take. Skip connections go through safe_concat (center-crop) so odd
+input sizes work.
 
 Loss head: the model returns logits. Train on them directly with
 ops.dice_loss_with_logits (num_class=1) or ops.cross_entropy on the
@@ -25,10 +29,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.bnorm import OpsBatchNorm3d
-from ..ops.conv import OpsConv3d, can_fuse_bn_conv, conv_bn3d
+from ..ops.conv import (OpsConv3d, can_fuse_bn_conv, can_fuse_upsample,
+                        conv_bn3d, upsample2_conv3d)
 from ..utils.tensorutils import safe_concat
 
 _FUSE_BN = os.environ.get('COINN_FUSE_BN', '1') == '1'
+_FUSE_UPSAMPLE = os.environ.get('COINN_FUSE_UPSAMPLE', '1') == '1'
 
 
 class _Block(nn.Module):
@@ -79,7 +85,10 @@ class UNet3D(nn.Module):
             x = d(x)
         for conv, block in zip(self.up_conv, self.up_block):
             skip = skips.pop()
-            x = F.interpolate(x, size=skip.shape[2:], mode='nearest')
-            x = conv(x)
+            if _FUSE_UPSAMPLE and can_fuse_upsample(conv, x, skip.shape[2:]):
+                x = upsample2_conv3d(x, conv.weight, conv.bias)
+            else:
+                x = F.interpolate(x, size=skip.shape[2:], mode='nearest')
+                x = conv(x)
             x = block(safe_concat(skip, x))
         return self.head(x)

@@ -7,6 +7,9 @@ runs through stock PyTorch — SURVEY.md §2.9):
     normalize-on-load instances, Cin=1 wgrad specialization, one-pass
     BN-backward + wgrad of the Cin=1 first layer) with implicit-GEMM
     fallbacks — conv3d_spatial.hip / conv3d.hip
+  - nearest-2x upsample + 3x3x3 conv (UNet3D decoder) as 8 parity classes
+    of summed-weight 2x2x2 convs from one low-res slab, the plain
+    upsample and its 2x2x2 brick-sum adjoint — upconv3d.hip
   - Conv2d fwd/dgrad/wgrad (ResNet): igemm (3x3 + 7x7 stem), spatial
     slab, tap-reuse + split-K wgrad, parity s2 dgrad — conv2d.hip
   - pointwise 1x1 convs as batched MFMA GEMMs     — pointwise.hip
@@ -414,3 +417,5 @@ def row_sum(m):
 
 # inference-time conv+BN folding (host-side; see ops/fuse.py)
 from .fuse import fold_bn, fuse_conv_bn_eval  # noqa: E402
+# nearest-2x upsample + conv facade (ops/conv.py, upconv3d.hip)
+from .conv import upsample2_conv3d  # noqa: E402

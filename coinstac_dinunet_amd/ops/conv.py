@@ -11,6 +11,9 @@ GPU paths (bf16):
   - stem_conv_bn3d: the Cin = 1 first conv, its BN and the second conv as
     one node — statistics from the first conv's epilogue, BN-backward and
     the first conv's wgrad as one pass over its output.
+  - upsample2_conv3d: nearest-2x upsample + 3x3x3/pad-1 conv (the UNet3D
+    decoder step) as 8 parity classes of 2x2x2 convs on the low-res input
+    (upconv3d.hip); the upsampled activation is neither written nor saved.
 CPU falls back to torch.nn.functional convs.
 """
 import os
@@ -86,18 +89,21 @@ def _dgrad3d(C, go, wb, in_shape, stride):
     return C.conv3d_dgrad(go, wb, in_shape, stride)
 
 
+def _fwd3d(C, xb, wb, stride):
+    route = route_fwd3d(xb.size(1), xb.size(3), xb.size(4), stride)
+    if route == 'igemm':
+        return C.conv3d_fwd(xb, wb, stride)
+    return C.conv3d_fwd_spatial(xb, wb, stride,
+                                1 if route == 'spatial-ctile1' else 0)
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride):
         C = require_native()
         xb = x.to(torch.bfloat16)
         wb = weight.to(torch.bfloat16)
-        route = route_fwd3d(xb.size(1), xb.size(3), xb.size(4), stride)
-        if route == 'igemm':
-            out = C.conv3d_fwd(xb, wb, stride)
-        else:
-            out = C.conv3d_fwd_spatial(xb, wb, stride,
-                                       1 if route == 'spatial-ctile1' else 0)
+        out = _fwd3d(C, xb, wb, stride)
         if bias is not None:
             out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
         ctx.save_for_backward(xb, wb)
@@ -123,6 +129,81 @@ class _Conv3dFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = C.channel_sum(go)
         return gx, gw, gb, None
+
+
+def route_upconv3d(cin, H, W):
+    """'collapsed' | 'composed' for nearest-2x upsample + 3x3x3 conv; H, W
+    are the LOW-RES input plane.
+
+    'collapsed' is upconv3d_fwd (64 summed-weight slots on the low-res
+    slab); 'composed' is upsample2_nearest3d followed by the plain forward
+    kernels, for channel counts below one MFMA k-step's worth and planes
+    the slab tiles do not fill. Every timed decoder shape runs 'collapsed'
+    faster than 'composed' (profiles/upconv_ab.md)."""
+    if cin >= 16 and W % 8 == 0 and H * W >= 64:
+        return 'collapsed'
+    return 'composed'
+
+
+class _UpConv3dFn(torch.autograd.Function):
+    """conv3d(upsample2_nearest(x), weight, padding=1) with only the LOW-RES
+    input saved. Backward goes through the adjoint of the upsample:
+    dx = fold2_sum3d(dgrad(go)), and the wgrad reads an upsampled temporary
+    that lives for that one call."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        C = require_native()
+        xb = x.to(torch.bfloat16)
+        wb = weight.to(torch.bfloat16)
+        if route_upconv3d(xb.size(1), xb.size(3), xb.size(4)) == 'collapsed':
+            out = C.upconv3d_fwd(xb, wb)
+        else:
+            out = _fwd3d(C, C.upsample2_nearest3d(xb), wb, 1)
+        if bias is not None:
+            out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
+        ctx.save_for_backward(xb, wb)
+        ctx.has_bias = bias is not None
+        ctx.in_dtype = x.dtype
+        ctx.w_dtype = weight.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        xb, wb = ctx.saved_tensors
+        go = grad_out.to(torch.bfloat16).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            up_shape = list(xb.shape[:2]) + [2 * s for s in xb.shape[2:]]
+            gx = C.fold2_sum3d(_dgrad3d(C, go, wb, up_shape,
+                                        1)).to(ctx.in_dtype)
+        if ctx.needs_input_grad[1]:
+            xu = C.upsample2_nearest3d(xb)
+            gw = C.conv3d_wgrad(xu, go, 1, 0).to(ctx.w_dtype)
+            del xu
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = C.channel_sum(go)
+        return gx, gw, gb
+
+
+def upsample2_conv3d(x, weight, bias=None):
+    """conv3d(nearest-2x upsample of x, weight[Cout,Cin,3,3,3], padding 1):
+    [N,Cin,D,H,W] -> [N,Cout,2D,2H,2W]. On GPU the HIP path (bf16 out, the
+    upsampled tensor never in HBM on the 'collapsed' route); torch on CPU."""
+    if x.is_cuda and native_available():
+        return _UpConv3dFn.apply(x, weight, bias)
+    return F.conv3d(F.interpolate(x, scale_factor=2, mode='nearest'), weight,
+                    bias, padding=1)
+
+
+def can_fuse_upsample(conv, x, size):
+    """True when interpolate(x, size, 'nearest') -> conv is an exact 2x
+    upsample into a stride-1 3x3x3 conv that upsample2_conv3d takes."""
+    return (x.is_cuda and native_available() and x.dim() == 5
+            and isinstance(conv, nn.Conv3d) and _is_3x3_family(conv)
+            and conv.stride[0] == 1
+            and tuple(size) == tuple(2 * s for s in x.shape[2:]))
 
 
 def _fused_fwd3d(C, xb, wb, bias, stride, ab):

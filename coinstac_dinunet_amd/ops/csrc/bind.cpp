@@ -80,6 +80,10 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
                                    std::vector<int64_t> in_shape);
 torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
                                       std::vector<int64_t> in_shape);
+// upconv3d.hip
+torch::Tensor upconv3d_fwd(torch::Tensor x, torch::Tensor w);
+torch::Tensor upsample2_nearest3d(torch::Tensor x);
+torch::Tensor fold2_sum3d(torch::Tensor g);
 // conv2d.hip
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
                          c10::optional<torch::Tensor> bn_ab);
@@ -168,6 +172,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "CTILE-1 forward + epilogue BN statistics");
   m.def("conv3d_dgrad_spatial", &conv3d_dgrad_spatial);
   m.def("conv3d_dgrad_s2_spatial", &conv3d_dgrad_s2_spatial);
+  m.def("upconv3d_fwd", &upconv3d_fwd,
+        "nearest-2x upsample + 3x3x3 conv, 8 parity classes from one slab");
+  m.def("upsample2_nearest3d", &upsample2_nearest3d);
+  m.def("fold2_sum3d", &fold2_sum3d, "2x2x2 brick sums: upsample2's adjoint");
   m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("bn_ab") = py::none());
   m.def("conv2d_dgrad", &conv2d_dgrad);
