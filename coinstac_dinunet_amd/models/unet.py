@@ -7,14 +7,24 @@ the external implementation repos).
 MI355X mapping: every conv is a 3x3x3/pad-1 stride-1 or stride-2
 OpsConv3d, so the whole encoder/decoder runs on the spatial-slab MFMA
 kernels; BN+ReLU are the fused bnorm kernels. Downsampling is stride-2
-convolution (not pooling) and upsampling is nearest-neighbor interp +
-conv, no transposed-conv kernel needed. Where the skip is exactly twice the
-decoder input (even sizes) the pair runs as ops.upsample2_conv3d: 8 parity
-classes of 2x2x2 convs on the low-res input (upconv3d.hip), so the 8x
-upsampled activation is never written, read or kept for backward.
-COINN_FUSE_UPSAMPLE=0 restores interpolate + conv, which odd skip sizes
-always take. Skip connections go through safe_concat (center-crop) so odd
-input sizes work.
+convolution (not pooling). Upsampling has two modes:
+
+up_mode='nearest' (default): nearest-neighbor interp + 3x3x3 conv. Where the
+skip is exactly twice the decoder input (even sizes) the pair runs as
+ops.upsample2_conv3d: 8 parity classes of 2x2x2 convs on the low-res input
+(upconv3d.hip), so the 8x upsampled activation is never written, read or
+kept for backward. COINN_FUSE_UPSAMPLE=0 restores interpolate + conv, which
+odd skip sizes always take.
+
+up_mode='transpose': the learned upsample of the original 3D U-Net, V-Net
+and nnU-Net, ConvTranspose3d(kernel 2, stride 2) with bias, as
+OpsConvTranspose3d on the deconv3d.hip kernels (same parameter names as
+nn.ConvTranspose3d, so such checkpoints load). Its output is exactly twice
+the decoder input; where the skip is smaller (odd encoder sizes) it is
+cropped to the skip before the concat.
+
+Skip connections go through safe_concat (center-crop) so odd input sizes
+work.
 
 Loss head: the model returns logits. Train on them directly with
 ops.dice_loss_with_logits (num_class=1) or ops.cross_entropy on the
@@ -29,8 +39,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.bnorm import OpsBatchNorm3d
-from ..ops.conv import (OpsConv3d, can_fuse_bn_conv, can_fuse_upsample,
-                        conv_bn3d, upsample2_conv3d)
+from ..ops.conv import (OpsConv3d, OpsConvTranspose3d, can_fuse_bn_conv,
+                        can_fuse_upsample, conv_bn3d, upsample2_conv3d)
 from ..utils.tensorutils import safe_concat
 
 _FUSE_BN = os.environ.get('COINN_FUSE_BN', '1') == '1'
@@ -60,15 +70,25 @@ class _Block(nn.Module):
 class UNet3D(nn.Module):
     """Encoder-decoder with skip connections; `widths` sets depth."""
 
-    def __init__(self, in_channels=1, num_class=2, widths=(16, 32, 64)):
+    def __init__(self, in_channels=1, num_class=2, widths=(16, 32, 64),
+                 up_mode='nearest'):
         super().__init__()
+        if up_mode not in ('nearest', 'transpose'):
+            raise ValueError(f"up_mode must be 'nearest' or 'transpose', "
+                             f'got {up_mode!r}')
+        self.up_mode = up_mode
         self.stem = _Block(in_channels, widths[0])
         self.down = nn.ModuleList(
             _Block(widths[i], widths[i + 1], stride=2)
             for i in range(len(widths) - 1))
-        self.up_conv = nn.ModuleList(
-            OpsConv3d(widths[i + 1], widths[i], 3, padding=1, bias=False)
-            for i in reversed(range(len(widths) - 1)))
+        if up_mode == 'transpose':
+            self.up_conv = nn.ModuleList(
+                OpsConvTranspose3d(widths[i + 1], widths[i], 2, stride=2)
+                for i in reversed(range(len(widths) - 1)))
+        else:
+            self.up_conv = nn.ModuleList(
+                OpsConv3d(widths[i + 1], widths[i], 3, padding=1, bias=False)
+                for i in reversed(range(len(widths) - 1)))
         self.up_block = nn.ModuleList(
             _Block(2 * widths[i], widths[i])
             for i in reversed(range(len(widths) - 1)))
@@ -85,7 +105,12 @@ class UNet3D(nn.Module):
             x = d(x)
         for conv, block in zip(self.up_conv, self.up_block):
             skip = skips.pop()
-            if _FUSE_UPSAMPLE and can_fuse_upsample(conv, x, skip.shape[2:]):
+            if self.up_mode == 'transpose':
+                x = conv(x)
+                sd, sh, sw = skip.shape[2:]
+                if tuple(x.shape[2:]) != (sd, sh, sw):
+                    x = x[..., :sd, :sh, :sw]
+            elif _FUSE_UPSAMPLE and can_fuse_upsample(conv, x, skip.shape[2:]):
                 x = upsample2_conv3d(x, conv.weight, conv.bias)
             else:
                 x = F.interpolate(x, size=skip.shape[2:], mode='nearest')

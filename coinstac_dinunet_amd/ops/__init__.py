@@ -10,6 +10,9 @@ runs through stock PyTorch — SURVEY.md §2.9):
   - nearest-2x upsample + 3x3x3 conv (UNet3D decoder) as 8 parity classes
     of summed-weight 2x2x2 convs from one low-res slab, the plain
     upsample and its 2x2x2 brick-sum adjoint — upconv3d.hip
+  - ConvTranspose3d kernel 2 / stride 2 (the learned U-Net upsample)
+    fwd/dgrad/wgrad: bf16 MFMA, all 8 parity classes from one staged tile,
+    packed interleaving stores, bias in the epilogue — deconv3d.hip
   - Conv2d fwd/dgrad/wgrad (ResNet): igemm (3x3 + 7x7 stem), spatial
     slab, tap-reuse + split-K wgrad, parity s2 dgrad — conv2d.hip
   - pointwise 1x1 convs as batched MFMA GEMMs     — pointwise.hip
@@ -419,3 +422,5 @@ def row_sum(m):
 from .fuse import fold_bn, fuse_conv_bn_eval  # noqa: E402
 # nearest-2x upsample + conv facade (ops/conv.py, upconv3d.hip)
 from .conv import upsample2_conv3d  # noqa: E402
+# transposed conv, kernel 2 / stride 2 (ops/conv.py, deconv3d.hip)
+from .conv import OpsConvTranspose3d, conv_transpose2x3d  # noqa: E402

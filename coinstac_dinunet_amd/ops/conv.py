@@ -14,6 +14,9 @@ GPU paths (bf16):
   - upsample2_conv3d: nearest-2x upsample + 3x3x3/pad-1 conv (the UNet3D
     decoder step) as 8 parity classes of 2x2x2 convs on the low-res input
     (upconv3d.hip); the upsampled activation is neither written nor saved.
+  - OpsConvTranspose3d / conv_transpose2x3d: ConvTranspose3d kernel 2 /
+    stride 2 (the learned decoder upsample) as 8 pointwise GEMMs per staged
+    tile, forward, dgrad and wgrad (deconv3d.hip).
 CPU falls back to torch.nn.functional convs.
 """
 import os
@@ -195,6 +198,69 @@ def upsample2_conv3d(x, weight, bias=None):
         return _UpConv3dFn.apply(x, weight, bias)
     return F.conv3d(F.interpolate(x, scale_factor=2, mode='nearest'), weight,
                     bias, padding=1)
+
+
+class _ConvTranspose2x3dFn(torch.autograd.Function):
+    """conv_transpose3d(x, weight[Cin,Cout,2,2,2], bias, stride=2) on
+    deconv3d.hip: kernel == stride, so each of the 8 output parity classes
+    is a pointwise GEMM of the low-res input; the bias is added in the
+    forward kernel's epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        C = require_native()
+        xb = x.to(torch.bfloat16)
+        wb = weight.to(torch.bfloat16)
+        out = C.deconv3d_fwd(xb, wb, bias)
+        ctx.save_for_backward(xb, wb)
+        ctx.has_bias = bias is not None
+        ctx.in_dtype = x.dtype
+        ctx.w_dtype = weight.dtype
+        ctx.b_dtype = bias.dtype if bias is not None else None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        xb, wb = ctx.saved_tensors
+        go = grad_out.to(torch.bfloat16).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = C.deconv3d_dgrad(go, wb, list(xb.shape)).to(ctx.in_dtype)
+        if ctx.needs_input_grad[1]:
+            gw = C.deconv3d_wgrad(xb, go).to(ctx.w_dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = C.channel_sum(go).to(ctx.b_dtype)
+        return gx, gw, gb
+
+
+def conv_transpose2x3d(x, weight, bias=None):
+    """conv_transpose3d(x, weight[Cin,Cout,2,2,2], bias, stride=2):
+    [N,Cin,D,H,W] -> [N,Cout,2D,2H,2W]. On GPU the HIP path (bf16 out);
+    torch on CPU."""
+    if x.is_cuda and native_available():
+        return _ConvTranspose2x3dFn.apply(x, weight, bias)
+    return F.conv_transpose3d(x, weight, bias, stride=2)
+
+
+class OpsConvTranspose3d(nn.ConvTranspose3d):
+    """nn.ConvTranspose3d (same parameters and state_dict keys) that runs
+    kernel 2 / stride 2 / no padding on the HIP path; anything else, and a
+    call with output_size, falls through to the library."""
+
+    def _is_2x(self):
+        return (self.kernel_size == (2, 2, 2) and self.stride == (2, 2, 2)
+                and self.padding == (0, 0, 0)
+                and self.output_padding == (0, 0, 0)
+                and self.dilation == (1, 1, 1) and self.groups == 1)
+
+    def forward(self, x, output_size=None):
+        if x.is_cuda and native_available() and output_size is None \
+                and x.dim() == 5 and self._is_2x():
+            return _ConvTranspose2x3dFn.apply(x, self.weight, self.bias)
+        if x.is_cuda and x.dtype != self.weight.dtype:
+            x = x.to(self.weight.dtype)
+        return super().forward(x, output_size)
 
 
 def can_fuse_upsample(conv, x, size):

@@ -84,6 +84,12 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
 torch::Tensor upconv3d_fwd(torch::Tensor x, torch::Tensor w);
 torch::Tensor upsample2_nearest3d(torch::Tensor x);
 torch::Tensor fold2_sum3d(torch::Tensor g);
+// deconv3d.hip
+torch::Tensor deconv3d_fwd(torch::Tensor x, torch::Tensor w,
+                           c10::optional<torch::Tensor> bias);
+torch::Tensor deconv3d_dgrad(torch::Tensor go, torch::Tensor w,
+                             std::vector<int64_t> in_shape);
+torch::Tensor deconv3d_wgrad(torch::Tensor x, torch::Tensor go);
 // conv2d.hip
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
                          c10::optional<torch::Tensor> bn_ab);
@@ -176,6 +182,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "nearest-2x upsample + 3x3x3 conv, 8 parity classes from one slab");
   m.def("upsample2_nearest3d", &upsample2_nearest3d);
   m.def("fold2_sum3d", &fold2_sum3d, "2x2x2 brick sums: upsample2's adjoint");
+  m.def("deconv3d_fwd", &deconv3d_fwd, py::arg("x"), py::arg("w"),
+        py::arg("bias") = py::none(),
+        "conv_transpose3d, kernel 2 / stride 2: 8 parity classes per block");
+  m.def("deconv3d_dgrad", &deconv3d_dgrad);
+  m.def("deconv3d_wgrad", &deconv3d_wgrad);
   m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("bn_ab") = py::none());
   m.def("conv2d_dgrad", &conv2d_dgrad);

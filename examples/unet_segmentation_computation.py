@@ -57,7 +57,9 @@ class SegTrainer(COINNTrainer):
         k = self.cache.get('num_class', 2)
         self.nn['unet'] = UNet3D(in_channels=1, num_class=1 if k == 2 else k,
                                  widths=tuple(self.cache.get('widths',
-                                                             (8, 16))))
+                                                             (8, 16))),
+                                 up_mode=self.cache.get('up_mode',
+                                                        'nearest'))
 
     def iteration(self, batch):
         dev = self.device['gpu']
@@ -101,7 +103,7 @@ def local_kw(args):
                 split_ratio=(0.5, 0.25, 0.25), data_dir='data',
                 num_class=args.classes, monitor_metric='f1',
                 metric_direction='maximize', seed_all=True,
-                patience=args.epochs, verbose=False)
+                patience=args.epochs, verbose=False, up_mode=args.up_mode)
 
 
 def run_loopback(args):
@@ -145,5 +147,9 @@ if __name__ == '__main__':
     ap.add_argument('--side', type=int, default=16)
     ap.add_argument('--classes', type=int, default=2,
                     help='2: binary dice head; K > 2: K-plane cross-entropy')
+    ap.add_argument('--up-mode', choices=['nearest', 'transpose'],
+                    default='nearest',
+                    help='decoder upsample: nearest + conv, or '
+                         'ConvTranspose3d(2, stride 2)')
     args = ap.parse_args()
     {'loopback': run_loopback, 'rccl': run_rccl}[args.mode](args)
