@@ -13,7 +13,9 @@ GPU paths (bf16):
     the first conv's wgrad as one pass over its output.
   - upsample2_conv3d: nearest-2x upsample + 3x3x3/pad-1 conv (the UNet3D
     decoder step) as 8 parity classes of 2x2x2 convs on the low-res input
-    (upconv3d.hip); the upsampled activation is neither written nor saved.
+    (upconv3d.hip); the upsampled activation is neither written nor saved,
+    and the backward (upconv3d_dgrad / upconv3d_wgrad) stays on the low-res
+    tile as well.
   - OpsConvTranspose3d / conv_transpose2x3d: ConvTranspose3d kernel 2 /
     stride 2 (the learned decoder upsample) as 8 pointwise GEMMs per staged
     tile, forward, dgrad and wgrad (deconv3d.hip).
@@ -148,11 +150,34 @@ def route_upconv3d(cin, H, W):
     return 'composed'
 
 
+def route_upconv3d_bwd(cin, cout, H, W):
+    """'collapsed' | 'composed' for the backward of nearest-2x upsample +
+    3x3x3 conv; H, W are the LOW-RES input plane.
+
+    'collapsed' is upconv3d_dgrad + upconv3d_wgrad on the 64 summed-weight
+    slots, both on the low-res tile; 'composed' is the stride-1 dgrad at
+    full resolution + fold2_sum3d and the plain wgrad on an upsampled
+    temporary. The rule is the forward's, with the same floor on the
+    channels of go (the dgrad's K): every timed decoder shape runs
+    'collapsed' faster than 'composed' by more than the block-to-block
+    spread (profiles/upconv_bwd_ab.md). COINN_UPCONV_BWD=composed (or
+    =collapsed), read at every call, forces that route:
+    tools/upconv_bench.py times both in one process with it."""
+    forced = os.environ.get('COINN_UPCONV_BWD')
+    if forced in ('composed', 'collapsed'):
+        return forced
+    if cin >= 16 and cout >= 16 and W % 8 == 0 and H * W >= 64:
+        return 'collapsed'
+    return 'composed'
+
+
 class _UpConv3dFn(torch.autograd.Function):
     """conv3d(upsample2_nearest(x), weight, padding=1) with only the LOW-RES
-    input saved. Backward goes through the adjoint of the upsample:
-    dx = fold2_sum3d(dgrad(go)), and the wgrad reads an upsampled temporary
-    that lives for that one call."""
+    input saved. On the 'collapsed' backward route dx and dw come from the
+    low-res kernels (upconv3d_dgrad / upconv3d_wgrad). The 'composed' route
+    goes through the adjoint of the upsample: dx = fold2_sum3d(dgrad(go)),
+    and the wgrad reads an upsampled temporary that lives for that one
+    call."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -177,6 +202,16 @@ class _UpConv3dFn(torch.autograd.Function):
         xb, wb = ctx.saved_tensors
         go = grad_out.to(torch.bfloat16).contiguous()
         gx = gw = gb = None
+        if route_upconv3d_bwd(xb.size(1), wb.size(0), xb.size(3),
+                              xb.size(4)) == 'collapsed':
+            if ctx.needs_input_grad[0]:
+                gx = C.upconv3d_dgrad(go, wb,
+                                      list(xb.shape)).to(ctx.in_dtype)
+            if ctx.needs_input_grad[1]:
+                gw = C.upconv3d_wgrad(xb, go).to(ctx.w_dtype)
+            if ctx.has_bias and ctx.needs_input_grad[2]:
+                gb = C.channel_sum(go)
+            return gx, gw, gb
         if ctx.needs_input_grad[0]:
             up_shape = list(xb.shape[:2]) + [2 * s for s in xb.shape[2:]]
             gx = C.fold2_sum3d(_dgrad3d(C, go, wb, up_shape,

@@ -82,6 +82,9 @@ torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
                                       std::vector<int64_t> in_shape);
 // upconv3d.hip
 torch::Tensor upconv3d_fwd(torch::Tensor x, torch::Tensor w);
+torch::Tensor upconv3d_dgrad(torch::Tensor go, torch::Tensor w,
+                             std::vector<int64_t> x_shape);
+torch::Tensor upconv3d_wgrad(torch::Tensor x, torch::Tensor go);
 torch::Tensor upsample2_nearest3d(torch::Tensor x);
 torch::Tensor fold2_sum3d(torch::Tensor g);
 // deconv3d.hip
@@ -180,6 +183,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3d_dgrad_s2_spatial", &conv3d_dgrad_s2_spatial);
   m.def("upconv3d_fwd", &upconv3d_fwd,
         "nearest-2x upsample + 3x3x3 conv, 8 parity classes from one slab");
+  m.def("upconv3d_dgrad", &upconv3d_dgrad,
+        "dx of upsample + conv on the low-res tile (64 slots, no fold)");
+  m.def("upconv3d_wgrad", &upconv3d_wgrad,
+        "dw of upsample + conv from 64 slot gradients, no upsampled x");
   m.def("upsample2_nearest3d", &upsample2_nearest3d);
   m.def("fold2_sum3d", &fold2_sum3d, "2x2x2 brick sums: upsample2's adjoint");
   m.def("deconv3d_fwd", &deconv3d_fwd, py::arg("x"), py::arg("w"),

@@ -20,6 +20,19 @@ time: 2 * M * Cout * Cin * slots with M the output positions, slots = 27
 backward of both versions is counted at 2 x 27). Peak extra memory is
 max_memory_allocated over one forward + backward above what was allocated
 before it. A run without a GPU fails.
+
+    python tools/upconv_bench.py --bwd [--out profiles/upconv_bwd_ab.md]
+
+times the backward instead, at the same shapes and in the same alternating
+blocks: forward + backward of upsample2_conv3d with the backward on the
+'composed' route (COINN_UPCONV_BWD=composed: full-resolution dgrad +
+fold2_sum3d, wgrad on an upsampled temporary) and on the 'collapsed' route
+(upconv3d_dgrad + upconv3d_wgrad), then each backward kernel alone against
+the composed calls it replaces. Weight prep is inside the timed calls. The
+table adds the max abs difference of dx and dw between the two routes and,
+per row, spread = (max - min) / median over its blocks; `clear` is whether
+the collapsed median beats the composed one by more than the larger of the
+two spreads, the rule route_upconv3d_bwd rests on.
 """
 import argparse
 import os
@@ -103,17 +116,99 @@ def versions(x, conv, go):
             'composed': (fwd_composed, None)}
 
 
+def bwd_versions(x, conv, go):
+    """{group: {name: fn}}: the rows of one group are compared."""
+    C = ops.require_native()
+    xb = x.detach()
+    wb = conv.weight.detach().to(torch.bfloat16)
+    up_shape = list(xb.shape[:2]) + [2 * s for s in xb.shape[2:]]
+
+    def step(route):
+        def fn():
+            os.environ['COINN_UPCONV_BWD'] = route
+            x.grad = None
+            conv.weight.grad = None
+            opsconv.upsample2_conv3d(x, conv.weight, None).backward(go)
+            return x.grad, conv.weight.grad
+        return fn
+
+    return {
+        'fwd+bwd': {'composed': step('composed'),
+                    'collapsed': step('collapsed')},
+        'dgrad': {'composed': lambda: C.fold2_sum3d(
+                      opsconv._dgrad3d(C, go, wb, up_shape, 1)),
+                  'collapsed': lambda: C.upconv3d_dgrad(go, wb,
+                                                        list(xb.shape))},
+        'wgrad': {'composed': lambda: C.conv3d_wgrad(
+                      C.upsample2_nearest3d(xb), go, 1, 0),
+                  'collapsed': lambda: C.upconv3d_wgrad(xb, go)},
+    }
+
+
+def main_bwd(args):
+    dev = torch.device('cuda:0')
+    lines = ['| shape | pass | backward | ms median | min..max | spread | '
+             'speed-up | clear | peak extra MiB | max abs diff dx | '
+             'max abs diff dw |',
+             '|---|---|---|---|---|---|---|---|---|---|---|']
+    for n, cin, cout, side in SHAPES:
+        x, conv, go = make_case(n, cin, cout, side, dev)
+        shape = f'{n}x{cin}->{cout} {side}^3->{2 * side}^3'
+        groups = bwd_versions(x, conv, go)
+        gc = [g.float().clone() for g in groups['fwd+bwd']['composed']()]
+        gn = [g.float().clone() for g in groups['fwd+bwd']['collapsed']()]
+        diff = [(a - b).abs().max().item() for a, b in zip(gc, gn)]
+        for gname, live in groups.items():
+            for fn in live.values():
+                for _ in range(5):
+                    fn()
+            torch.cuda.synchronize()
+            times = {k: [] for k in live}
+            for _ in range(args.repeats):
+                for k, fn in live.items():
+                    times[k].append(time_block(fn, args.iters))
+            med = {k: statistics.median(t) for k, t in times.items()}
+            spread = {k: (max(t) - min(t)) / med[k]
+                      for k, t in times.items()}
+            gain = 1 - med['collapsed'] / med['composed']
+            clear = gain > max(spread.values())
+            for k, fn in live.items():
+                t = times[k]
+                new = k == 'collapsed'
+                lines.append(
+                    f'| {shape} | {gname} | {k} | {med[k]:.4f} | '
+                    f'{min(t):.4f}..{max(t):.4f} | {spread[k]:.3f} | '
+                    + (f"{med['composed'] / med[k]:.2f}x | "
+                       f"{'yes' if clear else 'NO'} | " if new else '- | - | ')
+                    + f'{peak_extra_bytes(fn) / 2**20:.1f} | '
+                    + (f'{diff[0]:.4g} | {diff[1]:.4g} |'
+                       if new and gname == 'fwd+bwd' else '- | - |'))
+        os.environ.pop('COINN_UPCONV_BWD', None)
+        del x, conv, go, groups, live, gc, gn
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--bwd', action='store_true',
+                    help='A/B the backward routes instead '
+                         '(default --out profiles/upconv_bwd_ab.md)')
     ap.add_argument('--iters', type=int, default=50,
                     help='calls per timed block')
     ap.add_argument('--repeats', type=int, default=5,
                     help='alternating blocks per version')
-    ap.add_argument('--out', default='profiles/upconv_ab.md',
-                    help='write the table here too')
+    ap.add_argument('--out', default=None,
+                    help='write the table here too '
+                         '(default profiles/upconv_ab.md)')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = ('profiles/upconv_bwd_ab.md' if args.bwd
+                    else 'profiles/upconv_ab.md')
     ops.require_native()
     dev = torch.device('cuda:0')
+    if args.bwd:
+        return write_table(args, main_bwd(args))
 
     lines = ['| shape | pass | version | route | ms median | min..max | '
              'TF/s | peak extra MiB | max abs diff vs A |',
@@ -155,7 +250,10 @@ def main():
                     f'{diff[k]:.4g} |')
         del x, conv, go, vers, live
         torch.cuda.empty_cache()
+    write_table(args, lines)
 
+
+def write_table(args, lines):
     text = '\n'.join(
         [f'calls per block: {args.iters}, blocks per version: '
          f'{args.repeats}, device: {torch.cuda.get_device_name(0)}', '']
