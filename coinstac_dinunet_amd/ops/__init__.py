@@ -424,3 +424,5 @@ from .fuse import fold_bn, fuse_conv_bn_eval  # noqa: E402
 from .conv import upsample2_conv3d  # noqa: E402
 # transposed conv, kernel 2 / stride 2 (ops/conv.py, deconv3d.hip)
 from .conv import OpsConvTranspose3d, conv_transpose2x3d  # noqa: E402
+# 3x3x3 conv, dense or dilated (ops/conv.py, conv3d_dilated.hip)
+from .conv import conv3d  # noqa: E402

@@ -136,6 +136,58 @@ class _Conv3dFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
+class _ConvDil3dFn(torch.autograd.Function):
+    """conv3d(x, weight[Cout,Cin,3,3,3], bias, padding=d, dilation=d) on
+    conv3d_dilated.hip. With stride 1 and padding == dilation the input
+    gradient is the same dilated conv of grad_out with tap-flipped,
+    transposed weights, so dx comes from the forward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dilation):
+        C = require_native()
+        xb = x.to(torch.bfloat16)
+        wb = weight.to(torch.bfloat16)
+        out = C.conv3d_dil_fwd(xb, wb, dilation)
+        if bias is not None:
+            out = out + bias.to(out.dtype).view(1, -1, 1, 1, 1)
+        ctx.save_for_backward(xb, wb)
+        ctx.dilation = dilation
+        ctx.has_bias = bias is not None
+        ctx.in_dtype = x.dtype
+        ctx.w_dtype = weight.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        xb, wb = ctx.saved_tensors
+        go = grad_out.to(torch.bfloat16).contiguous()
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = C.conv3d_dil_dgrad(go, wb, list(xb.shape),
+                                    ctx.dilation).to(ctx.in_dtype)
+        if ctx.needs_input_grad[1]:
+            gw = C.conv3d_dil_wgrad(xb, go, ctx.dilation).to(ctx.w_dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = C.channel_sum(go)
+        return gx, gw, gb, None
+
+
+# dilations conv3d_dilated.hip takes (its slab tiles are sized for these)
+DILATION_MIN, DILATION_MAX = 2, 16
+
+
+def _dilated_3x3x3(conv):
+    """The dilation d when `conv` is 3x3x3 / stride 1 / dilation == padding
+    == (d, d, d) with d in [2, 16] / groups 1, else 0."""
+    d = conv.dilation[0]
+    if (conv.kernel_size == (3, 3, 3) and conv.stride == (1, 1, 1)
+            and conv.dilation == (d, d, d) and conv.padding == (d, d, d)
+            and DILATION_MIN <= d <= DILATION_MAX and conv.groups == 1):
+        return int(d)
+    return 0
+
+
 def route_upconv3d(cin, H, W):
     """'collapsed' | 'composed' for nearest-2x upsample + 3x3x3 conv; H, W
     are the LOW-RES input plane.
@@ -615,7 +667,18 @@ class _ConvPw3dFn(torch.autograd.Function):
         return gx, gw, gb
 
 
-def conv3d(x, weight, bias=None, stride=1):
+def conv3d(x, weight, bias=None, stride=1, dilation=1):
+    """3x3x3 conv with padding == dilation. dilation 1: stride 1 or 2 on the
+    dense kernels; dilation in [2, 16] (stride 1): the dilated kernels."""
+    dilation = int(dilation)
+    if dilation != 1:
+        if stride != 1:
+            raise ValueError('a dilated conv3d is stride 1')
+        if x.is_cuda and native_available() \
+                and weight.shape[2:] == (3, 3, 3) \
+                and DILATION_MIN <= dilation <= DILATION_MAX:
+            return _ConvDil3dFn.apply(x, weight, bias, dilation)
+        return F.conv3d(x, weight, bias, padding=dilation, dilation=dilation)
     if x.is_cuda and native_available() and weight.shape[2:] == (3, 3, 3):
         return _Conv3dFn.apply(x, weight, bias, int(stride))
     return F.conv3d(x, weight, bias, stride=stride, padding=1)
@@ -698,14 +761,19 @@ class OpsConv2d(nn.Conv2d):
 class OpsConv3d(nn.Conv3d):
     """nn.Conv3d that runs the MFMA implicit-GEMM kernels on GPU.
 
-    Only 3x3x3/pad-1/stride-{1,2} routes to the HIP path; anything else
-    falls through to the library conv.
+    3x3x3/pad-1/stride-{1,2}, 3x3x3/stride-1 with dilation == padding in
+    [2, 16], and 1x1x1 route to the HIP path; anything else falls through
+    to the library conv.
     """
 
     def forward(self, x):
         if x.is_cuda and native_available() and _is_3x3_family(self):
             return _Conv3dFn.apply(x, self.weight, self.bias,
                                    int(self.stride[0]))
+        if x.is_cuda and native_available() and x.dim() == 5 \
+                and _dilated_3x3x3(self):
+            return _ConvDil3dFn.apply(x, self.weight, self.bias,
+                                      _dilated_3x3x3(self))
         if (x.is_cuda and native_available()
                 and self.kernel_size == (1, 1, 1)
                 and self.padding == (0, 0, 0)

@@ -80,6 +80,11 @@ torch::Tensor conv3d_dgrad_spatial(torch::Tensor go, torch::Tensor w,
                                    std::vector<int64_t> in_shape);
 torch::Tensor conv3d_dgrad_s2_spatial(torch::Tensor go, torch::Tensor w,
                                       std::vector<int64_t> in_shape);
+// conv3d_dilated.hip
+torch::Tensor conv3d_dil_fwd(torch::Tensor x, torch::Tensor w, int64_t d);
+torch::Tensor conv3d_dil_dgrad(torch::Tensor go, torch::Tensor w,
+                               std::vector<int64_t> in_shape, int64_t d);
+torch::Tensor conv3d_dil_wgrad(torch::Tensor x, torch::Tensor go, int64_t d);
 // upconv3d.hip
 torch::Tensor upconv3d_fwd(torch::Tensor x, torch::Tensor w);
 torch::Tensor upconv3d_dgrad(torch::Tensor go, torch::Tensor w,
@@ -181,6 +186,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "CTILE-1 forward + epilogue BN statistics");
   m.def("conv3d_dgrad_spatial", &conv3d_dgrad_spatial);
   m.def("conv3d_dgrad_s2_spatial", &conv3d_dgrad_s2_spatial);
+  m.def("conv3d_dil_fwd", &conv3d_dil_fwd,
+        "3x3x3 conv, dilation d = padding in [2, 16], sub-lattice slab");
+  m.def("conv3d_dil_dgrad", &conv3d_dil_dgrad);
+  m.def("conv3d_dil_wgrad", &conv3d_dil_wgrad,
+        "tap-reuse wgrad of the dilated conv, sliced fp32 partials");
   m.def("upconv3d_fwd", &upconv3d_fwd,
         "nearest-2x upsample + 3x3x3 conv, 8 parity classes from one slab");
   m.def("upconv3d_dgrad", &upconv3d_dgrad,
