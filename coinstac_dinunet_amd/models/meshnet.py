@@ -17,23 +17,28 @@ ConfusionMatrix.add_logits.
 
 Parameter names are those of a plain nn.Sequential of nn.Conv3d /
 nn.BatchNorm3d (/ nn.Dropout3d) modules, so such a state dict loads.
+
+norm='group' (min(norm_groups, channels) groups) or 'instance' replaces the
+BatchNorm by the per-sample norms of ops/groupnorm.py, ReLU fused, at the
+same positions (nn.GroupNorm / affine nn.InstanceNorm3d parameter names).
 """
 import torch.nn as nn
 
-from ..ops.bnorm import OpsBatchNorm3d
+from ..ops.groupnorm import norm_relu3d
 from ..ops.conv import OpsConv3d
 
 
 class MeshNet(nn.Module):
     def __init__(self, in_channels=1, num_class=2, channels=32,
-                 dilations=(1, 2, 4, 8, 16, 8, 4, 2, 1), dropout=0.0):
+                 dilations=(1, 2, 4, 8, 16, 8, 4, 2, 1), dropout=0.0,
+                 norm='batch', norm_groups=8):
         super().__init__()
         layers = []
         c_in = in_channels
         for d in dilations:
             layers.append(OpsConv3d(c_in, channels, 3, padding=d, dilation=d,
                                     bias=False))
-            layers.append(OpsBatchNorm3d(channels, relu=True))
+            layers.append(norm_relu3d(norm, channels, norm_groups))
             if dropout > 0:
                 layers.append(nn.Dropout3d(dropout))
             c_in = channels

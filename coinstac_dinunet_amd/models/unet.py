@@ -38,7 +38,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.bnorm import OpsBatchNorm3d
+from ..ops.groupnorm import norm_relu3d
 from ..ops.conv import (OpsConv3d, OpsConvTranspose3d, can_fuse_bn_conv,
                         can_fuse_upsample, conv_bn3d, upsample2_conv3d)
 from ..utils.tensorutils import safe_concat
@@ -53,13 +53,13 @@ class _Block(nn.Module):
     On GPU the inner (b1 -> c2) pair runs as one normalize-on-load fused
     conv (conv_bn3d), so b1's normalized activation never hits HBM."""
 
-    def __init__(self, cin, cout, stride=1):
+    def __init__(self, cin, cout, stride=1, norm='batch', norm_groups=8):
         super().__init__()
         self.c1 = OpsConv3d(cin, cout, 3, stride=stride, padding=1,
                             bias=False)
-        self.b1 = OpsBatchNorm3d(cout, relu=True)
+        self.b1 = norm_relu3d(norm, cout, norm_groups)
         self.c2 = OpsConv3d(cout, cout, 3, stride=1, padding=1, bias=False)
-        self.b2 = OpsBatchNorm3d(cout, relu=True)
+        self.b2 = norm_relu3d(norm, cout, norm_groups)
 
     def forward(self, x):
         if _FUSE_BN and can_fuse_bn_conv(self.b1, self.c2, x):
@@ -68,18 +68,25 @@ class _Block(nn.Module):
 
 
 class UNet3D(nn.Module):
-    """Encoder-decoder with skip connections; `widths` sets depth."""
+    """Encoder-decoder with skip connections; `widths` sets depth.
+
+    norm='batch' (default), 'group' (min(norm_groups, C) groups) or
+    'instance' picks the fused norm + ReLU of every block; the per-sample
+    norms (ops/groupnorm.py) keep no batch statistics, which suits sites
+    with differently distributed data. They run as separate passes, not on
+    the normalize-on-load path."""
 
     def __init__(self, in_channels=1, num_class=2, widths=(16, 32, 64),
-                 up_mode='nearest'):
+                 up_mode='nearest', norm='batch', norm_groups=8):
         super().__init__()
         if up_mode not in ('nearest', 'transpose'):
             raise ValueError(f"up_mode must be 'nearest' or 'transpose', "
                              f'got {up_mode!r}')
         self.up_mode = up_mode
-        self.stem = _Block(in_channels, widths[0])
+        nk = dict(norm=norm, norm_groups=norm_groups)
+        self.stem = _Block(in_channels, widths[0], **nk)
         self.down = nn.ModuleList(
-            _Block(widths[i], widths[i + 1], stride=2)
+            _Block(widths[i], widths[i + 1], stride=2, **nk)
             for i in range(len(widths) - 1))
         if up_mode == 'transpose':
             self.up_conv = nn.ModuleList(
@@ -90,7 +97,7 @@ class UNet3D(nn.Module):
                 OpsConv3d(widths[i + 1], widths[i], 3, padding=1, bias=False)
                 for i in reversed(range(len(widths) - 1)))
         self.up_block = nn.ModuleList(
-            _Block(2 * widths[i], widths[i])
+            _Block(2 * widths[i], widths[i], **nk)
             for i in reversed(range(len(widths) - 1)))
         # 1x1x1 head runs on the pointwise HIP kernel (accepts the fused-BN
         # path's bf16 activations; the stock fp32 nn.Conv3d head crashed on

@@ -13,7 +13,7 @@ import os
 
 import torch.nn as nn
 
-from ..ops.bnorm import OpsBatchNorm3d
+from ..ops.groupnorm import norm_relu3d
 from ..ops.conv import (OpsConv3d, can_fuse_bn_conv, can_fuse_stem,
                         conv_bn3d, stem_conv_bn3d)
 
@@ -29,25 +29,35 @@ _FUSE_STEM = os.environ.get('COINN_FUSE_STEM', '1') == '1'
 
 
 class _ConvBlock(nn.Module):
-    def __init__(self, cin, cout, stride=1):
+    def __init__(self, cin, cout, stride=1, norm='batch', norm_groups=8):
         super().__init__()
         self.conv = OpsConv3d(cin, cout, 3, stride=stride, padding=1, bias=False)
-        self.bn = OpsBatchNorm3d(cout, relu=True)  # ReLU fused into BN pass
+        # ReLU fused into the norm pass
+        self.bn = norm_relu3d(norm, cout, norm_groups)
 
     def forward(self, x):
         return self.bn(self.conv(x))
 
 
 class VBMNet(nn.Module):
-    """~9-layer 3D CNN: 1 -> widths[0] -> ... with stride-2 stages."""
+    """~9-layer 3D CNN: 1 -> widths[0] -> ... with stride-2 stages.
 
-    def __init__(self, in_channels=1, num_class=2, widths=(32, 64, 128, 256)):
+    norm='group' (min(norm_groups, C) groups) or 'instance' swaps every
+    BatchNorm for the per-sample norm of ops/groupnorm.py (ReLU fused); the
+    blocks then run composed, not on the fused BN chain."""
+
+    def __init__(self, in_channels=1, num_class=2, widths=(32, 64, 128, 256),
+                 norm='batch', norm_groups=8):
         super().__init__()
+        # the default passes no norm arguments: a block class swapped in for
+        # _ConvBlock (the stock-library baseline) takes (cin, cout, stride)
+        nk = ({} if norm == 'batch'
+              else dict(norm=norm, norm_groups=norm_groups))
         stages = []
         cin = in_channels
         for i, w in enumerate(widths):
-            stages.append(_ConvBlock(cin, w, stride=1 if i == 0 else 2))
-            stages.append(_ConvBlock(w, w))
+            stages.append(_ConvBlock(cin, w, stride=1 if i == 0 else 2, **nk))
+            stages.append(_ConvBlock(w, w, **nk))
             cin = w
         self.features = nn.Sequential(*stages)
         self.pool = nn.AdaptiveAvgPool3d(1)

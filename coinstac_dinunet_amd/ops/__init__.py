@@ -18,6 +18,9 @@ runs through stock PyTorch — SURVEY.md §2.9):
   - pointwise 1x1 convs as batched MFMA GEMMs     — pointwise.hip
   - fused BatchNorm(+ReLU[+residual]) fwd/bwd, stats-only, one-launch
     finalize of the conv-epilogue partials          — bnorm.hip
+  - GroupNorm / InstanceNorm(+ReLU / LeakyReLU) fwd/bwd over [N, C, S...]:
+    split-row Chan/Welford statistics merged in the consumers' prologue,
+    no atomics, backward from the saved input — groupnorm.hip
   - single-launch multi-tensor Adam / SGD         (K4) — adam.hip
   - flat gradient bucket pack / unpack            (K5/K7) — pack.hip
   - fused log_softmax + NLL loss fwd/bwd + argmax (K3/K16) — lsnll.hip
@@ -426,3 +429,6 @@ from .conv import upsample2_conv3d  # noqa: E402
 from .conv import OpsConvTranspose3d, conv_transpose2x3d  # noqa: E402
 # 3x3x3 conv, dense or dilated (ops/conv.py, conv3d_dilated.hip)
 from .conv import conv3d  # noqa: E402
+# GroupNorm / InstanceNorm with a fused activation (ops/groupnorm.py)
+from .groupnorm import (OpsGroupNorm, OpsInstanceNorm3d,  # noqa: E402
+                        group_norm)

@@ -142,6 +142,15 @@ std::vector<torch::Tensor> bn3d_bwd(torch::Tensor dy, torch::Tensor x,
                                     torch::Tensor mean_rstd,
                                     torch::Tensor gamma, torch::Tensor beta,
                                     bool relu);
+// groupnorm.hip
+std::vector<torch::Tensor> gn_fwd(torch::Tensor x, torch::Tensor gamma,
+                                  torch::Tensor beta, int64_t G, double eps,
+                                  bool act, double slope);
+std::vector<torch::Tensor> gn_bwd(torch::Tensor dy, torch::Tensor x,
+                                  torch::Tensor mean_rstd,
+                                  torch::Tensor gamma, torch::Tensor beta,
+                                  int64_t G, bool act, double slope);
+int64_t gn_splits(int64_t len, int64_t rows);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adam_flat", &fused_adam_flat, "single-kernel Adam on flat arenas");
@@ -227,4 +236,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one-launch BN finalize of the conv-epilogue partials");
   m.def("bn3d_infer", &bn3d_infer);
   m.def("bn3d_bwd", &bn3d_bwd);
+  m.def("gn_fwd", &gn_fwd,
+        "GroupNorm / InstanceNorm + (leaky) ReLU over [N, C, S...] bf16: "
+        "(y, mean_rstd[N*G][2])");
+  m.def("gn_bwd", &gn_bwd, "(dx, dgamma, dbeta) from the saved x");
+  m.def("gn_splits", &gn_splits,
+        "chunks a run of `len` elements is cut into when `rows` runs are "
+        "reduced (statistics: L, N*G; backward: S, N*C)");
 }
