@@ -12,7 +12,9 @@ MI355X mapping: the d = 1 layers are the dense spatial-slab kernels, the
 d >= 2 layers the sub-lattice slab kernels of conv3d_dilated.hip (forward,
 dgrad, wgrad), BN+ReLU the fused bnorm kernels and the head the pointwise
 kernel. Like UNet3D the model returns logits: train with ops.cross_entropy
-or ops.dice_loss_with_logits, count with Prf1a.add_logits /
+or ops.dice_loss_with_logits, or with ops.softmax_dice_loss (multi-class
+soft-dice + CE, segdice.hip) for parcellation labels; count with
+Prf1a.add_logits /
 ConfusionMatrix.add_logits.
 
 Parameter names are those of a plain nn.Sequential of nn.Conv3d /

@@ -28,7 +28,8 @@ work.
 
 Loss head: the model returns logits. Train on them directly with
 ops.dice_loss_with_logits (num_class=1) or ops.cross_entropy on the
-[N, C, D, H, W] logits (num_class > 1), and count with
+[N, C, D, H, W] logits (num_class > 1), or ops.softmax_dice_loss for
+multi-class soft-dice + CE (ops/csrc/segdice.hip), and count with
 Prf1a.add_logits / ConfusionMatrix.add_logits — on GPU these are the fused
 kernels of ops/csrc/segloss.hip, with no probability or prediction tensor.
 """

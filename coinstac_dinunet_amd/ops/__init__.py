@@ -28,6 +28,10 @@ runs through stock PyTorch — SURVEY.md §2.9):
   - segmentation head from logits: binary soft-dice fwd/bwd, voxelwise
     softmax cross-entropy fwd/bwd over [N, C, S...], tp/fp/tn/fn and
     KxK confusion without a prediction tensor — segloss.hip
+  - multi-class soft-dice (+ cross-entropy) loss from [N, C, S...] logits,
+    2 <= C <= 128, fwd/bwd: softmax in registers (C <= 8) or in an fp32
+    LDS tile (C <= 128), per-class sums without float atomics, one exp per
+    logit in each direction — segdice.hip
   - MFMA linear fwd (fused bias+ReLU) + dgrad + split-K wgrad (K2),
     parallel colsum — linear.hip
   - fused Gram-Schmidt for PowerSGD               (K8) — linear.hip
@@ -296,6 +300,89 @@ def dice_loss_with_logits(logits, target, beta=1.0, weights=None, eps=1e-5):
                                      float(beta), float(eps))
     from ..metrics.loss import dice_loss_binary
     return dice_loss_binary(torch.sigmoid(logits), target, beta, weights, eps)
+
+
+# ---- multi-class soft-dice (+CE) from logits (segdice.hip) -------------------
+SOFTMAX_DICE_MAX_CLASSES = 128
+
+
+class _SoftmaxDice(torch.autograd.Function):
+    """Saves the logits, the fp32 log-sum-exp per voxel and the per-row
+    (a_r, b_r) table of the finish kernel; no probability tensor."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ce_weight, include_background,
+                batch_dice, eps):
+        C = require_native()
+        loss, lse, coef = C.seg_sdice_fwd(logits, target, ce_weight,
+                                          include_background, batch_dice, eps)
+        ctx.save_for_backward(logits, target, lse, coef)
+        ctx.ce_weight = ce_weight
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        C = require_native()
+        logits, target, lse, coef = ctx.saved_tensors
+        g = C.seg_sdice_bwd(logits, target, lse, coef, grad_out,
+                            ctx.ce_weight)
+        return g, None, None, None, None, None
+
+
+def softmax_dice_loss(logits, target, ce_weight=0.0, include_background=True,
+                      batch_dice=False, eps=1e-5):
+    """Multi-class soft-dice loss over softmax probabilities, plus
+    `ce_weight` times the voxelwise cross-entropy, straight from logits.
+
+    logits [N, C, S...] with 2 <= C <= 128 (bf16, fp16 or fp32), target
+    [N, S...] class indices (uint8, bool or int64; other integer widths are
+    widened). A voxel whose label is outside [0, C) is dropped: it adds to
+    no sum and its gradients are exactly zero. With p = softmax(logits, 1)
+    and y the one-hot labels, a row is (n, c) (or c over the whole batch
+    with `batch_dice`) and
+
+        dice_r = (2 sum p y + eps) / (sum p + sum y + eps)
+        loss   = 1 - mean_r dice_r + ce_weight * CE
+
+    `include_background=False` leaves the class-0 rows out of the mean (the
+    softmax is still over all C). CE is summed over the kept voxels and
+    divided by N*S, the denominator of ops.cross_entropy. Equals
+    dice_loss_multiclass(softmax(logits), ...) + ce_weight * cross_entropy.
+
+    On GPU two HIP kernels give the 0-dim fp32 loss (segdice.hip) and one
+    writes the gradient in the logits' dtype; nothing synchronises the host
+    and two calls return bit-identical results. The gradient goes to
+    `logits` only."""
+    if logits.dim() < 3:
+        raise ValueError(f'logits must be [N, C, S...], got '
+                         f'{tuple(logits.shape)}')
+    C = logits.shape[1]
+    if C == 1:
+        raise ValueError('softmax_dice_loss needs C >= 2 class planes; for '
+                         'one logit plane use dice_loss_with_logits')
+    if C > SOFTMAX_DICE_MAX_CLASSES:
+        raise ValueError(f'softmax_dice_loss serves at most '
+                         f'{SOFTMAX_DICE_MAX_CLASSES} classes, got {C}')
+    target = _index_labels(target).detach()
+    if target.numel() * C != logits.numel():
+        raise ValueError('target must be [N, S...] with the logits\' '
+                         'batch and spatial extent')
+    if logits.is_cuda:
+        require_native()
+        return _SoftmaxDice.apply(logits, target, float(ce_weight),
+                                  bool(include_background), bool(batch_dice),
+                                  float(eps))
+    from ..metrics.loss import dice_loss_multiclass
+    x = logits.float()
+    loss = dice_loss_multiclass(torch.softmax(x, dim=1), target,
+                                include_background, batch_dice, eps)
+    if ce_weight:
+        t = target.long()
+        keep = (t >= 0) & (t < C)
+        nll = -torch.log_softmax(x, dim=1).gather(
+            1, t.clamp(0, C - 1).unsqueeze(1)).squeeze(1)
+        loss = loss + ce_weight * (nll * keep).sum() / t.numel()
+    return loss
 
 
 def seg_prf1a_counts(logits, target):

@@ -1,7 +1,7 @@
 """In-tree build of the gfx950 HIP extension (no hipify, no JIT cache).
 
 Drives hipcc directly: each csrc/*.hip (and bind.cpp) is compiled with
---offload-arch=gfx950 and linked against libtorch into
+--offload-arch=gfx950, several files at a time, and linked against libtorch into
 coinstac_dinunet_amd/ops/_hip_ops.so — the .so lives in the source tree so
 it travels with repo snapshots.
 """
@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 import sysconfig
+from concurrent.futures import ThreadPoolExecutor
 
 import torch
 from torch.utils import cpp_extension as ce
@@ -57,18 +58,26 @@ def build(verbose=True, force=False):
     lib_dir = ce.library_paths()[0]
     cflags = compile_flags()
 
-    objs = []
+    objs, stale = [], []
     build_dir = os.path.join(HERE, 'build')
     os.makedirs(build_dir, exist_ok=True)
     for src in sources:
         obj = os.path.join(build_dir,
                            os.path.basename(src).rsplit('.', 1)[0] + '.o')
         if force or _newer([src] + headers, obj):
-            cmd = ['hipcc', '-c', src, '-o', obj] + cflags
-            if verbose:
-                print('[ops.build]', ' '.join(cmd[:4]), '...', flush=True)
-            subprocess.run(cmd, check=True)
+            stale.append(['hipcc', '-c', src, '-o', obj] + cflags)
         objs.append(obj)
+
+    def compile_one(cmd):
+        if verbose:
+            print('[ops.build]', ' '.join(cmd[:4]), '...', flush=True)
+        subprocess.run(cmd, check=True)
+
+    # the files are independent (most of each compile is the torch headers):
+    # one hipcc per file, MAX_JOBS or up to 16 at a time
+    jobs = int(os.environ.get('MAX_JOBS', 0)) or min(16, os.cpu_count() or 1)
+    with ThreadPoolExecutor(max_workers=max(1, jobs)) as pool:
+        list(pool.map(compile_one, stale))
 
     link = (['hipcc', '-shared', '-fPIC', '-o', OUT_SO] + objs +
             [f'-L{lib_dir}', '-ltorch', '-ltorch_cpu', '-ltorch_hip',

@@ -47,6 +47,15 @@ torch::Tensor seg_ce_bwd(torch::Tensor logits, torch::Tensor target,
 torch::Tensor seg_prf1a_counts(torch::Tensor logits, torch::Tensor target);
 torch::Tensor seg_confusion_matrix(torch::Tensor logits, torch::Tensor target,
                                    int64_t num_classes);
+// segdice.hip
+std::vector<torch::Tensor> seg_sdice_fwd(torch::Tensor logits,
+                                         torch::Tensor target,
+                                         double ce_weight,
+                                         bool include_background,
+                                         bool batch_dice, double eps);
+torch::Tensor seg_sdice_bwd(torch::Tensor logits, torch::Tensor target,
+                            torch::Tensor lse, torch::Tensor coef,
+                            torch::Tensor grad_out, double ce_weight);
 // linear.hip
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor weight,
                          torch::Tensor bias, bool relu);
@@ -169,6 +178,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("seg_ce_bwd", &seg_ce_bwd);
   m.def("seg_prf1a_counts", &seg_prf1a_counts);
   m.def("seg_confusion_matrix", &seg_confusion_matrix);
+  m.def("seg_sdice_fwd", &seg_sdice_fwd,
+        "(loss, lse[N,S], coef[R,2]) of the multi-class soft-dice (+CE) loss");
+  m.def("seg_sdice_bwd", &seg_sdice_bwd);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_dgrad", &linear_dgrad);
   m.def("linear_wgrad", &linear_wgrad);
