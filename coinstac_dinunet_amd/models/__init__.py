@@ -1,7 +1,9 @@
+from .icalstm import ICALstm
 from .meshnet import MeshNet
 from .mlp import FreeSurferMLP
 from .resnet import ResNet18
 from .unet import UNet3D
 from .vbm import VBMNet
 
-__all__ = ['FreeSurferMLP', 'VBMNet', 'ResNet18', 'UNet3D', 'MeshNet']
+__all__ = ['FreeSurferMLP', 'VBMNet', 'ResNet18', 'UNet3D', 'MeshNet',
+           'ICALstm']

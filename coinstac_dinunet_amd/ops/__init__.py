@@ -34,6 +34,12 @@ runs through stock PyTorch — SURVEY.md §2.9):
     logit in each direction — segdice.hip
   - MFMA linear fwd (fused bias+ReLU) + dgrad + split-K wgrad (K2),
     parallel colsum — linear.hip
+  - persistent (bi)LSTM recurrence, 1 <= H <= 256: all T steps of a layer
+    in one launch per direction pair, fwd and reverse-time bwd; W_hh as
+    prepacked bf16 MFMA fragments held in registers (Hp <= 128) or streamed
+    from L2, h through a double-buffered LDS tile, c and the four gates of
+    a unit in one lane's fp32 registers; the time-parallel GEMMs on
+    linear.hip — lstm.hip
   - fused Gram-Schmidt for PowerSGD               (K8) — linear.hip
   - fused deflated power iteration + rowsum       (K10/K11) — rankdad.hip
 
@@ -519,3 +525,5 @@ from .conv import conv3d  # noqa: E402
 # GroupNorm / InstanceNorm with a fused activation (ops/groupnorm.py)
 from .groupnorm import (OpsGroupNorm, OpsInstanceNorm3d,  # noqa: E402
                         group_norm)
+# (bi)LSTM on the persistent recurrence kernels (ops/rnn.py, lstm.hip)
+from .rnn import OpsLSTM, lstm  # noqa: E402

@@ -63,6 +63,17 @@ torch::Tensor linear_dgrad(torch::Tensor go, torch::Tensor weight);
 torch::Tensor linear_wgrad(torch::Tensor go, torch::Tensor x);
 torch::Tensor colsum(torch::Tensor g);
 void gram_schmidt(torch::Tensor m, double eps);
+// lstm.hip
+torch::Tensor lstm_pack_weights(torch::Tensor w_hh);
+std::vector<torch::Tensor> lstm_rec_fwd(torch::Tensor xp, torch::Tensor wpack,
+                                        c10::optional<torch::Tensor> h0,
+                                        c10::optional<torch::Tensor> c0,
+                                        int64_t H, bool save);
+std::vector<torch::Tensor> lstm_rec_bwd(torch::Tensor dy, torch::Tensor dhT,
+                                        torch::Tensor dcT, torch::Tensor gates,
+                                        torch::Tensor cells,
+                                        c10::optional<torch::Tensor> c0,
+                                        torch::Tensor wpack);
 // conv3d.hip
 torch::Tensor mfma_probe_gemm(torch::Tensor A, torch::Tensor B);
 torch::Tensor conv3d_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
@@ -186,6 +197,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_wgrad", &linear_wgrad);
   m.def("colsum", &colsum);
   m.def("gram_schmidt", &gram_schmidt);
+  m.def("lstm_pack_weights", &lstm_pack_weights,
+        "W_hh [4H, H] -> [2, 4 Hp^2] bf16 MFMA fragments (forward, backward)");
+  m.def("lstm_rec_fwd", &lstm_rec_fwd,
+        "(y, h_T, c_T, gates, cells) of one LSTM layer's recurrence in one "
+        "launch; xp is [T, B, D, H, 4], gate innermost");
+  m.def("lstm_rec_bwd", &lstm_rec_bwd,
+        "(dG, dh0, dc0): the reverse-time loop of lstm_rec_fwd");
   m.def("mfma_probe_gemm", &mfma_probe_gemm);
   m.def("conv3d_fwd", &conv3d_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("bn_ab") = py::none());
