@@ -1,4 +1,5 @@
 from .icalstm import ICALstm
+from .icatransformer import ICATransformer
 from .meshnet import MeshNet
 from .mlp import FreeSurferMLP
 from .resnet import ResNet18
@@ -6,4 +7,4 @@ from .unet import UNet3D
 from .vbm import VBMNet
 
 __all__ = ['FreeSurferMLP', 'VBMNet', 'ResNet18', 'UNet3D', 'MeshNet',
-           'ICALstm']
+           'ICALstm', 'ICATransformer']

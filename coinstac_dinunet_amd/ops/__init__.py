@@ -40,6 +40,12 @@ runs through stock PyTorch — SURVEY.md §2.9):
     from L2, h through a double-buffered LDS tile, c and the four gates of
     a unit in one lane's fp32 registers; the time-parallel GEMMs on
     linear.hip — lstm.hip
+  - fused multi-head attention, 1 <= head_dim <= 128, key padding mask and
+    causal: S^T = K Q^T on the MFMA so that the softmaxed accumulators are
+    the operand of the second product, online softmax in registers, no
+    [Tq, Tk] tensor; backward as one-writer dK/dV and dQ kernels without
+    atomics; strided q, k, v straight from the packed in-projection on
+    linear.hip — attention.hip
   - fused Gram-Schmidt for PowerSGD               (K8) — linear.hip
   - fused deflated power iteration + rowsum       (K10/K11) — rankdad.hip
 
@@ -527,3 +533,6 @@ from .groupnorm import (OpsGroupNorm, OpsInstanceNorm3d,  # noqa: E402
                         group_norm)
 # (bi)LSTM on the persistent recurrence kernels (ops/rnn.py, lstm.hip)
 from .rnn import OpsLSTM, lstm  # noqa: E402
+# fused multi-head attention (ops/attention.py, attention.hip)
+from .attention import (ATTENTION_MAX_HEAD_DIM,  # noqa: E402
+                        OpsMultiheadAttention, attention)

@@ -74,6 +74,21 @@ std::vector<torch::Tensor> lstm_rec_bwd(torch::Tensor dy, torch::Tensor dhT,
                                         torch::Tensor cells,
                                         c10::optional<torch::Tensor> c0,
                                         torch::Tensor wpack);
+// attention.hip
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v,
+                                    c10::optional<torch::Tensor> mask,
+                                    bool causal, double scale);
+torch::Tensor attn_delta(torch::Tensor o, torch::Tensor dout);
+std::vector<torch::Tensor> attn_bwd_dkv(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor dout,
+                                        c10::optional<torch::Tensor> mask,
+                                        torch::Tensor lse, torch::Tensor delta,
+                                        bool causal, double scale);
+torch::Tensor attn_bwd_dq(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                          torch::Tensor dout,
+                          c10::optional<torch::Tensor> mask, torch::Tensor lse,
+                          torch::Tensor delta, bool causal, double scale);
 // conv3d.hip
 torch::Tensor mfma_probe_gemm(torch::Tensor A, torch::Tensor B);
 torch::Tensor conv3d_fwd(torch::Tensor x, torch::Tensor w, int64_t stride,
@@ -204,6 +219,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "launch; xp is [T, B, D, H, 4], gate innermost");
   m.def("lstm_rec_bwd", &lstm_rec_bwd,
         "(dG, dh0, dc0): the reverse-time loop of lstm_rec_fwd");
+  m.def("attn_fwd", &attn_fwd,
+        "(O [B, Tq, heads, Dh], lse [B, heads, Tq]) of fused attention over "
+        "strided q, k, v [B, heads, T, Dh]");
+  m.def("attn_delta", &attn_delta, "rowsum(dO * O), fp32 [B, heads, Tq]");
+  m.def("attn_bwd_dkv", &attn_bwd_dkv,
+        "(dK, dV) [B, Tk, heads, Dh]: one block per key tile, no atomics");
+  m.def("attn_bwd_dq", &attn_bwd_dq,
+        "dQ [B, Tq, heads, Dh]: one block per query tile, no atomics");
   m.def("mfma_probe_gemm", &mfma_probe_gemm);
   m.def("conv3d_fwd", &conv3d_fwd, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("bn_ab") = py::none());
