@@ -247,7 +247,8 @@ def cross_entropy(logits, target):
     if logits.is_cuda and native_available():
         if logits.dim() > 2:
             return _VoxelCrossEntropy.apply(logits, _index_labels(target))
-        return _FusedLogSoftmaxNLL.apply(logits, target)
+        # the classifier-head kernels read int64 labels only
+        return _FusedLogSoftmaxNLL.apply(logits, _index_labels(target).long())
     return torch.nn.functional.cross_entropy(logits, target)
 
 

@@ -10,6 +10,9 @@
 
 struct AdamHyper {
   float lr, beta1, beta2, eps, weight_decay;
+  // 1 - beta, rounded from the double: 1.0f - (float)0.999 is off by
+  // 1.3e-5 of its value, and so was every term entering v
+  float omb1, omb2;
   float bias1, bias2;  // 1 - beta^t corrections
 };
 
@@ -30,8 +33,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
     for (int k = 0; k < 4; ++k) {
       float pp = (&pv.x)[k], gg = (&gv.x)[k];
       gg += h.weight_decay * pp;
-      float mm = h.beta1 * (&mv.x)[k] + (1.0f - h.beta1) * gg;
-      float vvk = h.beta2 * (&vv.x)[k] + (1.0f - h.beta2) * gg * gg;
+      float mm = h.beta1 * (&mv.x)[k] + h.omb1 * gg;
+      float vvk = h.beta2 * (&vv.x)[k] + h.omb2 * gg * gg;
       float mhat = mm * inv_b1;
       float vhat = vvk * inv_b2;
       pp -= h.lr * mhat / (sqrtf(vhat) + h.eps);
@@ -48,8 +51,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
        i += (int64_t)gridDim.x * blockDim.x) {
     float pp = p[i], gg = g[i];
     gg += h.weight_decay * pp;
-    float mm = h.beta1 * m[i] + (1.0f - h.beta1) * gg;
-    float vv = h.beta2 * v[i] + (1.0f - h.beta2) * gg * gg;
+    float mm = h.beta1 * m[i] + h.omb1 * gg;
+    float vv = h.beta2 * v[i] + h.omb2 * gg * gg;
     p[i] = pp - h.lr * (mm * (1.0f / h.bias1)) /
                     (sqrtf(vv * (1.0f / h.bias2)) + h.eps);
     m[i] = mm;
@@ -89,8 +92,10 @@ static AdamHyper make_hyper(double lr, double beta1, double beta2, double eps,
   h.beta2 = (float)beta2;
   h.eps = (float)eps;
   h.weight_decay = (float)weight_decay;
-  h.bias1 = 1.0f - powf((float)beta1, (float)step);
-  h.bias2 = 1.0f - powf((float)beta2, (float)step);
+  h.omb1 = (float)(1.0 - beta1);
+  h.omb2 = (float)(1.0 - beta2);
+  h.bias1 = (float)(1.0 - std::pow(beta1, (double)step));
+  h.bias2 = (float)(1.0 - std::pow(beta2, (double)step));
   return h;
 }
 
@@ -114,8 +119,8 @@ __global__ void adam_mt_kernel(const int64_t* __restrict__ ptrs,
   for (int64_t i = off + threadIdx.x; i < end; i += blockDim.x) {
     float pp = p[i], gg = g[i];
     gg += h.weight_decay * pp;
-    float mm = h.beta1 * m[i] + (1.0f - h.beta1) * gg;
-    float vv = h.beta2 * v[i] + (1.0f - h.beta2) * gg * gg;
+    float mm = h.beta1 * m[i] + h.omb1 * gg;
+    float vv = h.beta2 * v[i] + h.omb2 * gg * gg;
     p[i] = pp - h.lr * (mm * inv_b1) / (sqrtf(vv * inv_b2) + h.eps);
     m[i] = mm;
     v[i] = vv;
@@ -126,7 +131,11 @@ void fused_adam_flat(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      torch::Tensor v, double lr, double beta1, double beta2,
                      double eps, double weight_decay, int64_t step) {
   CHECK_GPU(p); CHECK_CONTIG(p); CHECK_CONTIG(g);
+  CHECK_CONTIG(m); CHECK_CONTIG(v);
   int64_t n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n,
+              "fused_adam_flat: p, g, m, v must have the same numel");
+  if (n == 0) return;
   auto h = make_hyper(lr, beta1, beta2, eps, weight_decay, step);
   hipStream_t stream = current_stream();
   hipLaunchKernelGGL(adam_kernel, dim3(elem_grid(n)), dim3(ELEM_BLOCK), 0,
@@ -136,6 +145,15 @@ void fused_adam_flat(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                                 v.data_ptr()), h);
 }
 
+// same shape, and the same stride in every dimension that has one (the
+// stride of a size-1 dimension places nothing)
+static bool same_layout(const torch::Tensor& a, const torch::Tensor& b) {
+  if (a.sizes() != b.sizes()) return false;
+  for (int64_t d = 0; d < a.dim(); ++d)
+    if (a.size(d) > 1 && a.stride(d) != b.stride(d)) return false;
+  return true;
+}
+
 void fused_adam(std::vector<torch::Tensor> params,
                 std::vector<torch::Tensor> grads,
                 std::vector<torch::Tensor> exp_avgs,
@@ -143,12 +161,12 @@ void fused_adam(std::vector<torch::Tensor> params,
                 double beta1, double beta2, double eps, double weight_decay,
                 int64_t step) {
   const int T = (int)params.size();
+  TORCH_CHECK(grads.size() == params.size() &&
+              exp_avgs.size() == params.size() &&
+              exp_avg_sqs.size() == params.size(),
+              "fused_adam: the four tensor lists must have the same length");
   if (T == 0) return;
-  AdamHyper h;
-  h.lr = (float)lr; h.beta1 = (float)beta1; h.beta2 = (float)beta2;
-  h.eps = (float)eps; h.weight_decay = (float)weight_decay;
-  h.bias1 = 1.0f - powf((float)beta1, (float)step);
-  h.bias2 = 1.0f - powf((float)beta2, (float)step);
+  const AdamHyper h = make_hyper(lr, beta1, beta2, eps, weight_decay, step);
 
   const int64_t chunk = 16384;
   auto ptrs_cpu = torch::empty({T, 5}, torch::dtype(torch::kInt64));
@@ -158,6 +176,25 @@ void fused_adam(std::vector<torch::Tensor> params,
     TORCH_CHECK(params[t].scalar_type() == torch::kFloat32 &&
                 grads[t].scalar_type() == torch::kFloat32,
                 "fused_adam wants fp32 params/grads");
+    TORCH_CHECK(exp_avgs[t].scalar_type() == torch::kFloat32 &&
+                exp_avg_sqs[t].scalar_type() == torch::kFloat32,
+                "fused_adam wants fp32 state");
+    // the kernel walks raw memory: all four streams must hold element i at
+    // the same place. The parameter may be any dense layout (channels-last
+    // too) as long as its state has the same strides; a gradient laid out
+    // differently (a transposed view, a contiguous grad of a channels-last
+    // parameter) is copied into the parameter's layout first.
+    TORCH_CHECK(params[t].is_cuda() &&
+                params[t].is_non_overlapping_and_dense(),
+                "fused_adam: parameters must be dense GPU tensors");
+    TORCH_CHECK(grads[t].sizes() == params[t].sizes(),
+                "fused_adam: grad/param shape mismatch");
+    TORCH_CHECK(same_layout(exp_avgs[t], params[t]) &&
+                same_layout(exp_avg_sqs[t], params[t]),
+                "fused_adam: state must have the parameter's shape and "
+                "strides");
+    if (!same_layout(grads[t], params[t]))
+      grads[t] = at::empty_like(params[t]).copy_(grads[t]);
     pc[t * 5 + 0] = (int64_t)params[t].data_ptr();
     pc[t * 5 + 1] = (int64_t)grads[t].data_ptr();
     pc[t * 5 + 2] = (int64_t)exp_avgs[t].data_ptr();
@@ -206,13 +243,27 @@ void fused_sgd(std::vector<torch::Tensor> params,
                std::vector<torch::Tensor> bufs, double lr, double momentum,
                double weight_decay) {
   hipStream_t stream = current_stream();
+  TORCH_CHECK(grads.size() == params.size() && bufs.size() == params.size(),
+              "fused_sgd: the three tensor lists must have the same length");
   for (size_t i = 0; i < params.size(); ++i) {
     auto p = params[i];
+    CHECK_GPU(p); CHECK_CONTIG(p);
+    TORCH_CHECK(grads[i].sizes() == p.sizes(),
+                "fused_sgd: grad/param shape mismatch");
     auto g = grads[i].to(torch::kFloat32).contiguous();
     int64_t n = p.numel();
+    if (n == 0) continue;
+    // the momentum buffer is read only when momentum != 0 (the optimizer
+    // passes the grad as a placeholder otherwise)
+    float* buf = nullptr;
+    if (momentum != 0.0) {
+      CHECK_CONTIG(bufs[i]);
+      TORCH_CHECK(bufs[i].numel() == n,
+                  "fused_sgd: buffer/param numel mismatch");
+      buf = bufs[i].data_ptr<float>();
+    }
     hipLaunchKernelGGL(sgd_kernel, dim3(elem_grid(n, 1)), dim3(ELEM_BLOCK), 0,
-                       stream, p.data_ptr<float>(), g.data_ptr<float>(),
-                       bufs[i].data_ptr<float>(), n, (float)lr,
-                       (float)momentum, (float)weight_decay);
+                       stream, p.data_ptr<float>(), g.data_ptr<float>(), buf,
+                       n, (float)lr, (float)momentum, (float)weight_decay);
   }
 }

@@ -144,13 +144,20 @@ static void launch_linear(const TA* A, const TB* B, const float* bias,
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor weight,
                          torch::Tensor bias, bool relu) {
   CHECK_GPU(x);
+  CHECK_GPU(weight);
+  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2,
+              "linear_fwd: x must be [M, K] and weight [N, K], got ",
+              x.dim(), "-D and ", weight.dim(), "-D (flatten the leading "
+              "dimensions of x first)");
   auto x2 = x.contiguous();
   auto w = weight.contiguous();
   bool has_bias = bias.numel() > 0;
   auto b = has_bias ? bias.to(torch::kFloat32).contiguous() : bias;
   int64_t M = x2.size(0), K = x2.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "weight/input K mismatch");
+  TORCH_CHECK(!has_bias || b.numel() == N, "linear_fwd: bias must be [N]");
   auto out = torch::empty({M, N}, x2.options());
+  if (M == 0 || N == 0) return out;  // a zero-sized grid is no launch
   auto stream = current_stream();
   const float* bp = has_bias ? b.data_ptr<float>() : nullptr;
 
@@ -283,11 +290,15 @@ static void launch_linear_bwd(const TA* A, const TB* B, TC* C, int M, int N,
 // gx[M,K] = go[M,N] @ W[N,K]; output dtype follows go.
 torch::Tensor linear_dgrad(torch::Tensor go, torch::Tensor weight) {
   CHECK_GPU(go);
+  CHECK_GPU(weight);
+  TORCH_CHECK(go.dim() == 2 && weight.dim() == 2,
+              "linear_dgrad: go must be [M, N] and weight [N, K]");
   auto g = go.contiguous();
   auto w = weight.to(g.scalar_type()).contiguous();
   int64_t M = g.size(0), N = g.size(1), K = w.size(1);
   TORCH_CHECK(w.size(0) == N, "weight/grad N mismatch");
   auto gx = torch::empty({M, K}, g.options());
+  if (M == 0 || K == 0) return gx;
   auto stream = current_stream();
   if (g.scalar_type() == torch::kFloat32) {
     launch_linear_bwd<float, float, float, false>(
@@ -309,10 +320,16 @@ torch::Tensor linear_dgrad(torch::Tensor go, torch::Tensor weight) {
 // Skinny output over a long contraction (the MLP shape) uses split-K.
 torch::Tensor linear_wgrad(torch::Tensor go, torch::Tensor x) {
   CHECK_GPU(go);
+  CHECK_GPU(x);
+  TORCH_CHECK(go.dim() == 2 && x.dim() == 2,
+              "linear_wgrad: go must be [M, N] and x [M, K]");
   auto g = go.contiguous();
   auto x2 = x.to(g.scalar_type()).contiguous();
   int64_t M = g.size(0), N = g.size(1), K = x2.size(1);
   TORCH_CHECK(x2.size(0) == M, "x/grad M mismatch");
+  // an empty batch contributes nothing (and would make kchunk 0 below)
+  if (M == 0 || N == 0 || K == 0)
+    return torch::zeros({N, K}, g.options().dtype(torch::kFloat32));
   auto stream = current_stream();
   int64_t tiles = ((N + BM - 1) / BM) * ((K + BN - 1) / BN);
   int nsplit = 1;
@@ -377,9 +394,11 @@ __global__ void colsum_kernel(const float* __restrict__ g,
 
 torch::Tensor colsum(torch::Tensor g) {
   CHECK_GPU(g);
+  TORCH_CHECK(g.dim() == 2, "colsum: g must be [M, N]");
   auto gc = g.to(torch::kFloat32).contiguous();
   int64_t M = gc.size(0), N = gc.size(1);
   auto out = torch::empty({N}, gc.options());
+  if (N == 0) return out;
   hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)N), dim3(ELEM_BLOCK),
                      0, current_stream(), gc.data_ptr<float>(),
                      out.data_ptr<float>(), M, N);

@@ -14,12 +14,14 @@ template <typename T>
 __global__ void lsnll_fwd_kernel(const T* __restrict__ logits,
                                  const int64_t* __restrict__ target,
                                  float* __restrict__ logprobs,
-                                 float* __restrict__ loss_partial, int64_t B,
+                                 double* __restrict__ loss_partial, int64_t B,
                                  int C) {
   const int wave = threadIdx.x / WAVE_SIZE;
   const int lane = threadIdx.x % WAVE_SIZE;
   const int waves_per_block = blockDim.x / WAVE_SIZE;
-  float local_loss = 0.0f;
+  // the sum over rows is kept in double: thousands of wave partials folded
+  // into one fp32 by atomics lost 2e-6 of the mean loss at B = 8195
+  double local_loss = 0.0;
   for (int64_t row = (int64_t)blockIdx.x * waves_per_block + wave; row < B;
        row += (int64_t)gridDim.x * waves_per_block) {
     const T* xrow = logits + row * C;
@@ -35,10 +37,13 @@ __global__ void lsnll_fwd_kernel(const T* __restrict__ logits,
     for (int off = WAVE_SIZE / 2; off > 0; off >>= 1)
       sum += __shfl_down(sum, off);
     sum = __shfl(sum, 0);
-    float lse = maxv + __logf(sum);
+    // (x - max) - log(sum), not x - (max + log(sum)): the latter rounds
+    // log(sum) to an ulp of max, 1e-3 for logits near 1e4
+    const float logsum = __logf(sum);
     for (int c = lane; c < C; c += WAVE_SIZE)
-      logprobs[row * C + c] = to_f32(xrow[c]) - lse;
-    if (lane == 0) local_loss += -(to_f32(xrow[target[row]]) - lse);
+      logprobs[row * C + c] = (to_f32(xrow[c]) - maxv) - logsum;
+    if (lane == 0)
+      local_loss += logsum - (to_f32(xrow[target[row]]) - maxv);
   }
   if (lane == 0) atomicAdd(loss_partial, local_loss);
 }
@@ -88,13 +93,21 @@ __global__ void argmax_rows_kernel(const T* __restrict__ x,
 std::vector<torch::Tensor> logsoftmax_nll_fwd(torch::Tensor logits,
                                               torch::Tensor target) {
   CHECK_GPU(logits);
+  CHECK_GPU(target);
+  TORCH_CHECK(logits.dim() == 2, "logsoftmax_nll_fwd: logits must be [B, C]");
   auto l = logits.contiguous();
   auto t = target.contiguous();
   int64_t B = l.size(0);
   int C = (int)l.size(1);
+  TORCH_CHECK(t.scalar_type() == torch::kInt64 && t.numel() == B,
+              "logsoftmax_nll_fwd: target must be B int64 class indices");
   auto logprobs = torch::empty({B, (int64_t)C},
                                l.options().dtype(torch::kFloat32));
-  auto loss = torch::zeros({}, l.options().dtype(torch::kFloat32));
+  if (B == 0)  // mean over no rows, as torch: NaN; nothing to launch
+    return {torch::full({}, NAN, l.options().dtype(torch::kFloat32)),
+            logprobs};
+  auto loss = torch::zeros({}, l.options().dtype(torch::kFloat64));
+  TORCH_CHECK(C > 0, "logsoftmax_nll_fwd: no classes");
   int waves_per_block = ELEM_BLOCK / WAVE_SIZE;
   int grid = (int)std::min<int64_t>((B + waves_per_block - 1) / waves_per_block,
                                     2048);
@@ -104,23 +117,29 @@ std::vector<torch::Tensor> logsoftmax_nll_fwd(torch::Tensor logits,
         hipLaunchKernelGGL(lsnll_fwd_kernel<scalar_t>, dim3(grid),
                            dim3(ELEM_BLOCK), 0, current_stream(),
                            l.data_ptr<scalar_t>(), t.data_ptr<int64_t>(),
-                           logprobs.data_ptr<float>(), loss.data_ptr<float>(),
+                           logprobs.data_ptr<float>(), loss.data_ptr<double>(),
                            B, C);
       });
-  loss.div_((double)B);
-  return {loss, logprobs};
+  return {loss.div_((double)B).to(torch::kFloat32), logprobs};
 }
 
 torch::Tensor logsoftmax_nll_bwd(torch::Tensor logprobs, torch::Tensor target,
                                  torch::Tensor grad_out,
                                  torch::ScalarType out_dtype) {
-  CHECK_GPU(logprobs);
+  CHECK_GPU(logprobs); CHECK_CONTIG(logprobs);
+  CHECK_GPU(target);
+  TORCH_CHECK(logprobs.dim() == 2,
+              "logsoftmax_nll_bwd: logprobs must be [B, C]");
   auto t = target.contiguous();
   int64_t B = logprobs.size(0);
   int C = (int)logprobs.size(1);
+  TORCH_CHECK(t.scalar_type() == torch::kInt64 && t.numel() == B,
+              "logsoftmax_nll_bwd: target must be B int64 class indices");
   auto g = grad_out.to(torch::kFloat32).contiguous();
+  TORCH_CHECK(g.numel() == 1, "logsoftmax_nll_bwd: grad_out must be a scalar");
   auto grad_logits = torch::empty({B, (int64_t)C},
                                   logprobs.options().dtype(out_dtype));
+  if (B * C == 0) return grad_logits;
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::ScalarType::Half, at::ScalarType::BFloat16, out_dtype, "lsnll_bwd",
       [&] {
@@ -135,10 +154,12 @@ torch::Tensor logsoftmax_nll_bwd(torch::Tensor logprobs, torch::Tensor target,
 
 torch::Tensor argmax_rows(torch::Tensor x) {
   CHECK_GPU(x);
+  TORCH_CHECK(x.dim() == 2, "argmax_rows: x must be [B, C]");
   auto l = x.contiguous();
   int64_t B = l.size(0);
   int C = (int)l.size(1);
   auto out = torch::empty({B}, l.options().dtype(torch::kInt64));
+  if (B == 0) return out;
   int waves_per_block = ELEM_BLOCK / WAVE_SIZE;
   int grid = (int)std::min<int64_t>((B + waves_per_block - 1) / waves_per_block,
                                     2048);

@@ -61,10 +61,14 @@ __global__ void confusion_kernel(const int64_t* __restrict__ pred,
 
 torch::Tensor prf1a_counts(torch::Tensor pred, torch::Tensor true_) {
   CHECK_GPU(pred);
+  CHECK_GPU(true_);
+  TORCH_CHECK(pred.numel() == true_.numel(),
+              "prf1a_counts: pred and true must have the same numel");
   auto p = pred.contiguous().to(torch::kInt64);
   auto t = true_.contiguous().to(torch::kInt64);
   int64_t n = p.numel();
   auto counts = torch::zeros({4}, p.options());
+  if (n == 0) return counts;
   hipLaunchKernelGGL(prf1a_kernel, dim3(elem_grid(n, 16)), dim3(ELEM_BLOCK),
                      0, current_stream(), p.data_ptr<int64_t>(),
                      t.data_ptr<int64_t>(), counts.data_ptr<int64_t>(), n);
@@ -74,6 +78,10 @@ torch::Tensor prf1a_counts(torch::Tensor pred, torch::Tensor true_) {
 torch::Tensor confusion_matrix(torch::Tensor pred, torch::Tensor true_,
                                int64_t num_classes) {
   CHECK_GPU(pred);
+  CHECK_GPU(true_);
+  TORCH_CHECK(pred.numel() == true_.numel(),
+              "confusion_matrix: pred and true must have the same numel");
+  TORCH_CHECK(num_classes >= 1, "confusion_matrix: num_classes must be >= 1");
   auto p = pred.contiguous().to(torch::kInt64);
   auto t = true_.contiguous().to(torch::kInt64);
   int64_t n = p.numel();
@@ -81,9 +89,12 @@ torch::Tensor confusion_matrix(torch::Tensor pred, torch::Tensor true_,
   auto mat = torch::zeros({num_classes, num_classes}, p.options());
   size_t smem = (size_t)K * K * sizeof(int);
   TORCH_CHECK(smem <= 160 * 1024, "num_classes too large for LDS histogram");
+  if (n == 0) return mat;
   hipLaunchKernelGGL(confusion_kernel, dim3(elem_grid(n, 16)),
                      dim3(ELEM_BLOCK), smem, current_stream(),
                      p.data_ptr<int64_t>(), t.data_ptr<int64_t>(),
                      mat.data_ptr<int64_t>(), n, K);
+  // above 64 KB of dynamic LDS a launch can be refused: read its status
+  HIP_OK(hipGetLastError());
   return mat;
 }

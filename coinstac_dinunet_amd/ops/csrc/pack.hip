@@ -22,7 +22,8 @@ __global__ void pack_kernel(const Seg* __restrict__ segs, int nseg,
                             float* __restrict__ flat, int64_t total) {
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
-    // binary search the segment containing i
+    // binary search the LAST segment with offset <= i: empty segments
+    // share their offset with the next one and are skipped that way
     int lo = 0, hi = nseg - 1;
     while (lo < hi) {
       int mid = (lo + hi + 1) >> 1;
@@ -45,13 +46,16 @@ __global__ void unpack_kernel(const Seg* __restrict__ segs, int nseg,
   }
 }
 
+// `total` is the flat buffer's numel: the kernels walk [0, total) and find
+// each element's segment, so the segments must cover exactly that range.
 static std::vector<Seg> build_segs(const std::vector<torch::Tensor>& ts,
-                                   bool as_dst) {
+                                   bool as_dst, int64_t total) {
   std::vector<Seg> segs;
   int64_t off = 0;
   for (auto& t : ts) {
-    TORCH_CHECK(t.is_contiguous() && t.scalar_type() == torch::kFloat32,
-                "pack/unpack expects contiguous fp32 tensors");
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                t.scalar_type() == torch::kFloat32,
+                "pack/unpack expects contiguous fp32 GPU tensors");
     Seg s;
     s.src = as_dst ? nullptr : t.data_ptr<float>();
     s.dst = as_dst ? t.data_ptr<float>() : nullptr;
@@ -60,6 +64,8 @@ static std::vector<Seg> build_segs(const std::vector<torch::Tensor>& ts,
     off += s.numel;
     segs.push_back(s);
   }
+  TORCH_CHECK(off == total, "pack/unpack: the flat buffer holds ", total,
+              " elements, the tensors ", off);
   return segs;
 }
 
@@ -74,8 +80,9 @@ static torch::Tensor upload_segs(const std::vector<Seg>& segs,
 
 void pack_tensors(std::vector<torch::Tensor> tensors, torch::Tensor flat) {
   CHECK_GPU(flat); CHECK_CONTIG(flat);
-  auto segs = build_segs(tensors, /*as_dst=*/false);
   int64_t total = flat.numel();
+  auto segs = build_segs(tensors, /*as_dst=*/false, total);
+  if (total == 0) return;
   auto dseg = upload_segs(segs, flat.device());
   hipLaunchKernelGGL(pack_kernel, dim3(elem_grid(total)), dim3(ELEM_BLOCK), 0,
                      current_stream(),
@@ -85,8 +92,9 @@ void pack_tensors(std::vector<torch::Tensor> tensors, torch::Tensor flat) {
 
 void unpack_tensors(torch::Tensor flat, std::vector<torch::Tensor> tensors) {
   CHECK_GPU(flat); CHECK_CONTIG(flat);
-  auto segs = build_segs(tensors, /*as_dst=*/true);
   int64_t total = flat.numel();
+  auto segs = build_segs(tensors, /*as_dst=*/true, total);
+  if (total == 0) return;
   auto dseg = upload_segs(segs, flat.device());
   hipLaunchKernelGGL(unpack_kernel, dim3(elem_grid(total)), dim3(ELEM_BLOCK),
                      0, current_stream(),

@@ -586,5 +586,7 @@ torch::Tensor seg_confusion_matrix(torch::Tensor logits, torch::Tensor target,
                            mat.data_ptr<int64_t>(), a.N, K, a.S);
     });
   });
+  // above 64 KB of dynamic LDS a launch can be refused: read its status
+  HIP_OK(hipGetLastError());
   return mat;
 }
